@@ -25,8 +25,14 @@ and, at N = 1 only (short records: throughput, host issue time, library launches
                backbone call): the non-network cost of the exchange
     search_vqa_unpad / train_vqa_unpad  the same steps with the RAGGED decoder stream (ops.set_unpad): the decoder operators
                on the valid region rows only; logits and gradients equal the padded computation's
-Every timed block is repeated `--repeats` times (default 5, same `--steps` each); `value` / `ms_per_step` are the
-MEDIAN block, `value_min` / `value_max` the slowest / fastest block.
+Each record times exactly `--steps` steps (bilevel: whole rounds of 6), issued back to back in one synchronised window
+and cut into `--repeats` blocks of consecutive steps by HIP events (default 5; at most one block per step); `value` /
+`ms_per_step` are the MEDIAN block's time per step, `value_min` / `value_max` the slowest / fastest block,
+`wall_ms_per_step` the whole window by the host clock.
+`--dump-outputs DIR`: after the timed steps of the headline record, what its last timed step handed its caller -- the
+loss, every parameter's gradient (norms, and a fixed seeded sample of the elements), the sampled operators -- is
+written as DIR/<name>.npy (float32 / float64, < 64 MB).  Inputs, weights and samplers are seeded: the same arguments
+give the same inputs on every run, so two builds can be compared output for output.
 Every record carries its own `roofline` (the fp32-MFMA GEMM kernel class, the dominant kernel, measured with HIP
 events on the launch stream over a repeat of the timed steps right after the timed region -- the events cost ~9 % of a
 step, so they stay out of the throughput measurement) and, at N = 1, its own `cpu_baseline` (the CPU oracle, a port of
@@ -351,6 +357,24 @@ def cpu_threads():
 
 
 LINE_LIMIT = 8000   # characters; the driver parses the last stdout line and keeps ~16 KB of it
+DUMP_SAMPLE = 1 << 22   # gradient elements drawn for --dump-outputs (16 MB of float32; all of them when there are fewer)
+DUMP_SEED = 20261015
+
+
+def block_sizes(calls, repeats):
+    """The `calls` timed calls as min(repeats, calls) blocks of consecutive calls, sizes differing by at most one."""
+    n = max(1, min(repeats, calls))
+    return [calls // n + (1 if i < calls % n else 0) for i in range(n)]
+
+
+def write_outputs(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 / float64 only, 64 MB at most in all."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values()) and total <= 64 << 20, total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 def _r(x, nd=4):
@@ -443,8 +467,13 @@ def main():
     ap.add_argument('--full-out', default=None, help='where the full record goes (default gpurun_out/bench_full.json)')
     ap.add_argument('--no-fixed-cost', action='store_true', help='skip the per-launch fixed-cost microbenchmark behind roofline.fixed_cost_share '
                     '(~1900 extra GEMM launches: keep them out of a kernel trace of the steps)')
-    ap.add_argument('--repeats', type=int, default=5, help='timed blocks of --steps steps each; value = the median block')
+    ap.add_argument('--repeats', type=int, default=5, help='blocks the --steps timed steps are split into; value = the median block')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="after the timed steps, write what the headline workload's last timed step computed (loss, gradients, "
+                         'sampled operators) as DIR/<name>.npy, float32 / float64, at most 64 MB')
     args = ap.parse_args()
+    if args.steps < 1 or args.repeats < 1:
+        ap.error('--steps and --repeats must be at least 1')
 
     env_world = os.environ.get('WORLD_SIZE')
     if env_world is None and args.gpus > 1:
@@ -823,7 +852,31 @@ def main():
             t = int(f.item() > 0)
         return t
 
-    def measure(wl, steps, warmup):
+    def net_of(wl):
+        base = wl[:-len('_unpad')] if wl.endswith('_unpad') else wl
+        key = {'train_vqa': 'train', 'train_vqa_dp1': 'train_dp1', 'search_vqa_dp1': 'search_dp1',
+               'search_vqa_dropin': 'dropin'}.get(base, base if base in EXTRA else 'search')
+        return state[key]['net']
+
+    def outputs_of(wl, loss):
+        """What the caller of the timed step holds after its last call: the loss, every parameter's `.grad` (zeros where
+        there is none) as float64 norms in named_parameters() order plus a fixed seeded sample of the concatenated elements
+        (all of them when they fit), and the operator each supernet cell sampled."""
+        net = net_of(wl)
+        grads = [p.grad if p.grad is not None else torch.zeros_like(p) for _, p in net.named_parameters()]
+        with torch.no_grad():
+            norms = torch.stack([g.double().norm() for g in grads])
+            flat = torch.cat([g.reshape(-1).float() for g in grads])
+            if flat.numel() > DUMP_SAMPLE:
+                idx = np.unique(np.random.RandomState(DUMP_SEED).randint(0, flat.numel(), DUMP_SAMPLE))
+                flat = flat[torch.from_numpy(idx).to(dev)]
+        out = {'loss': np.array([float(loss.detach())], np.float64), 'grad_norms': norms.cpu().numpy(),
+               'grad_sample': flat.cpu().numpy()}
+        if hasattr(net, 'redundant_modules'):
+            out['sampled_ops'] = np.array([m.active_index[0] for m in net.redundant_modules], np.float64)
+        return out
+
+    def measure(wl, steps, warmup, dump=None):
         step, fl, per_call = make_step(wl)
         calls = max(1, steps // per_call) if per_call > 1 else steps
         wcalls = max(1, warmup // per_call) if per_call > 1 else warmup
@@ -858,24 +911,31 @@ def main():
             with open(os.environ['MMNAS_BENCH_HOST_PROFILE'] + '.' + wl, 'w') as f:
                 pstats.Stats(pr, stream=f).sort_stats('tottime').print_stats(45)
                 pstats.Stats(pr, stream=f).sort_stats('cumulative').print_stats(60)
-        # `repeats` timed blocks of exactly `calls` calls each, every block bracketed by barrier + synchronize on both
-        # sides; the reported block is the MEDIAN (a 0.1 s block on a fresh box is at the mercy of clock ramps)
+        # exactly `calls` timed calls (= `steps` steps), issued back to back between one barrier + synchronize on each side
+        # (wall clock) and cut into `repeats` blocks of consecutive calls by HIP events on the launch stream -- markers only,
+        # the queue never drains between blocks; the reported block is the MEDIAN by time per step (a short window on a
+        # fresh box is at the mercy of clock ramps).  (Re-synchronising per block would charge every block the ~0.7 ms of
+        # an empty queue filling up again: +4 % per step at 4-step blocks.)
         nsteps = calls * per_call
-        blocks = []
-        rank_el = []
-        rep = 0
-        while rep < max(1, args.repeats):
-            fl[0] = 0.0
+        sizes = block_sizes(calls, args.repeats)
+        while True:
+            marks = [torch.cuda.Event(enable_timing=True) for _ in range(len(sizes) + 1)]
+            block_flops = []
             barrier()
             t0 = time.perf_counter()
-            for _ in range(calls):
-                loss = step()
-            t_enq = time.perf_counter() - t0   # host time to issue the steps (close to `elapsed` = host-bound)
+            marks[0].record()
+            for i, n in enumerate(sizes):
+                fl[0] = 0.0
+                for _ in range(n):
+                    loss = step()
+                marks[i + 1].record()
+                block_flops.append(fl[0] / (n * per_call))
+            t_enq = time.perf_counter() - t0   # host time to issue the steps (close to `wall` = host-bound)
             barrier()
-            el = time.perf_counter() - t0
+            wall = time.perf_counter() - t0
             # the persistent LSTM's hand-off gives up (and poisons the pass with NaN) when a workgroup of its grid was not
-            # resident -- e.g. a collective's kernel held the slot: read the flag after EVERY block.  A block that saw one (on
-            # any rank) is not a measurement: all ranks fall back to nn.LSTM together, re-warm, and the blocks start over
+            # resident -- e.g. a collective's kernel held the slot: read the flag after the timed steps.  If they saw one (on
+            # any rank) they are not a measurement: all ranks fall back to nn.LSTM together, re-warm, and time them again
             if lstm_timed_out_any():
                 if os.environ.get('MMNAS_LSTM', '1') != '0':
                     os.environ['MMNAS_LSTM'] = '0'
@@ -884,20 +944,27 @@ def main():
                         step()
                     barrier()
                     lstm_timed_out_any()
-                    blocks, rank_el, rep = [], [], 0
                     continue
                 multi['lstm_timed_out'] += 1          # (cannot happen: the fallback has no hand-off; reported if it does)
-            if world > 1:
-                mine = torch.zeros(world, device=dev, dtype=torch.float64)
-                mine[rank] = el
-                dist.all_reduce(mine)                      # every rank's own time (the line's time is their maximum)
-                rank_el.append([float(v) for v in mine])
-                el = max(rank_el[-1])
-            blocks.append((el, t_enq, fl[0]))
-            rep += 1
+            break
+        # seconds per step of every block; N > 1: every rank's own, the line's time is their maximum
+        mine = torch.tensor([marks[i].elapsed_time(marks[i + 1]) * 1e-3 / (n * per_call) for i, n in enumerate(sizes)],
+                            dtype=torch.float64)
+        rank_el = None
+        if world > 1:
+            allr = torch.zeros(world, len(sizes), device=dev, dtype=torch.float64)
+            allr[rank] = mine.to(dev)
+            dist.all_reduce(allr)
+            rank_el = allr.cpu().t().tolist()            # [block][rank]
+            w = torch.tensor([wall], device=dev, dtype=torch.float64)
+            dist.all_reduce(w, op=dist.ReduceOp.MAX)
+            wall = float(w)
+        blocks = [(max(r), t_enq / nsteps, f) for r, f in zip(rank_el or [[float(v)] for v in mine], block_flops)]
+        # the last timed step has just finished: what it left its caller (nothing has run since)
+        outputs = outputs_of(wl, loss) if dump else None
         order = sorted(range(len(blocks)), key=lambda i: blocks[i][0])
-        elapsed, t_enqueue, timed_flops = blocks[order[len(order) // 2]]
-        el_min, el_max = blocks[order[0]][0], blocks[order[-1]][0]
+        spp, enq_pp, flops_pp = blocks[order[len(order) // 2]]          # seconds, host seconds, flops per step
+        spp_min, spp_max = blocks[order[0]][0], blocks[order[-1]][0]
         # host time of ONE call issued into an EMPTY queue (synchronise first): in the timed blocks the host runs ahead
         # until the launch queue is full and then waits on it, so there `host_issue` approaches the GPU time of a
         # GPU-bound step; this is what the host itself needs
@@ -928,23 +995,29 @@ def main():
             stats = {n: dict(ms=arr[i].ms, flops=arr[i].flops, bytes=arr[i].bytes, launches=arr[i].launches)
                      for i, n in enumerate(L.K_NAMES)}
         rec = {
-            'metric': METRICS[wl], 'value': world * nsteps / elapsed, 'unit': 'steps/s',
-            'steps': nsteps, 'warmup': wcalls * per_call, 'ms_per_step': 1000.0 * elapsed / nsteps,
-            'repeats': len(blocks), 'value_min': world * nsteps / el_max, 'value_max': world * nsteps / el_min,
-            'value_note': 'median of `repeats` timed blocks of `steps` steps each; value_min / value_max = slowest / fastest block',
-            'blocks_ms_per_step': [round(1000.0 * b[0] / nsteps, 4) for b in blocks],   # in the order they ran
+            'metric': METRICS[wl], 'value': world / spp, 'unit': 'steps/s',
+            'steps': nsteps, 'warmup': wcalls * per_call, 'ms_per_step': 1000.0 * spp,
+            'repeats': len(blocks), 'value_min': world / spp_max, 'value_max': world / spp_min,
+            'value_note': 'median of the `repeats` blocks (HIP events on the launch stream) of the `steps` timed steps, which run '
+                          'back to back; value_min / value_max = slowest / fastest block; wall_ms_per_step = all of them by the '
+                          'host clock, synchronised on both sides',
+            'wall_ms_per_step': 1000.0 * wall / nsteps,
+            'blocks_steps': [n * per_call for n in sizes],
+            'blocks_ms_per_step': [round(1000.0 * b[0], 4) for b in blocks],   # in the order they ran
             'workload': WORKLOADS[wl],
-            'samples_per_s': world * nsteps * (state[wl]['B'] if wl in EXTRA else B) / elapsed,
-            'algorithmic_tflops_per_gpu': timed_flops / elapsed / 1e12,
-            'step_frac_of_mfma_peak': timed_flops / elapsed / 1e12 / PEAK_MFMA_F32_TFLOPS,
+            'samples_per_s': world * (state[wl]['B'] if wl in EXTRA else B) / spp,
+            'algorithmic_tflops_per_gpu': flops_pp / spp / 1e12,
+            'step_frac_of_mfma_peak': flops_pp / spp / 1e12 / PEAK_MFMA_F32_TFLOPS,
             'final_loss': float(loss.detach()),
-            'host_issue_ms_per_step': 1000.0 * t_enqueue / nsteps,
+            'host_issue_ms_per_step': 1000.0 * enq_pp,
             'host_issue_ms_per_step_empty_queue': host_alone_ms,
         }
+        if outputs is not None:
+            rec['outputs'] = {k: list(v.shape) for k, v in outputs.items()}
         if world > 1:
             mid = order[len(order) // 2]
-            rec['rank_ms_per_step'] = [round(1000.0 * v / nsteps, 4) for v in rank_el[mid]]   # of the median block, by rank
-            rec['rank_ms_per_step_blocks'] = [[round(1000.0 * v / nsteps, 4) for v in row] for row in rank_el]
+            rec['rank_ms_per_step'] = [round(1000.0 * v, 4) for v in rank_el[mid]]   # of the median block, by rank
+            rec['rank_ms_per_step_blocks'] = [[round(1000.0 * v, 4) for v in row] for row in rank_el]
         if stats and wl in N1_SUBS and not wl.endswith('_unpad'):
             psteps = prof_calls * per_call
             rec['library_launches_per_step'] = sum(s_['launches'] for s_ in stats.values()) / psteps
@@ -979,7 +1052,7 @@ def main():
                                # share of the TIMED step (the un-instrumented blocks `value` comes from); the roofline pass
                                # itself runs 15-25 % longer per step (a completion signal per dispatch), so the share of
                                # THAT pass is kept under its own name
-                               'share_of_step_time': (gm['ms'] / psteps) / (1000.0 * elapsed / nsteps),
+                               'share_of_step_time': (gm['ms'] / psteps) / (1000.0 * spp),
                                'share_of_instrumented_pass': gm['ms'] * 1e-3 / prof_elapsed}
             if wl in ('search_vqa', 'arch_vqa', 'bilevel_vqa', 'train_vqa') and world == 1 and not args.no_fixed_cost:
                 # What limits the class: at d = 256 a launch is ~4.5 us of fixed cost around 8 K-tiles, and halving the MFMA
@@ -1015,6 +1088,8 @@ def main():
             rec['roofline_pass'] = {'steps': psteps, 'ms_per_step': 1000.0 * prof_elapsed / psteps,
                                     'kernel_ms_per_step': tot_ms / psteps,
                                     'note': 'same steps repeated after the timed region with per-launch HIP events'}
+        if outputs is not None and rank == 0:
+            write_outputs(dump, outputs)
         return rec
 
     recs = {}
@@ -1030,7 +1105,7 @@ def main():
             except Exception as e:   # noqa: BLE001
                 recs[wl] = {'metric': METRICS[wl], 'value': None, 'error': '%s: %s' % (type(e).__name__, str(e)[:300])}
         else:
-            recs[wl] = measure(wl, steps, warm)
+            recs[wl] = measure(wl, steps, warm, dump=args.dump_outputs if wl == wanted[0] else None)
     for wl, ref in (('search_vqa_stream', 'search_vqa'), ('search_vqa_dp1', 'search_vqa'), ('train_vqa_dp1', 'train_vqa'),
                     ('search_vqa_unpad', 'search_vqa'), ('train_vqa_unpad', 'train_vqa')):
         if recs.get(wl, {}).get('value') and recs.get(ref, {}).get('value'):

@@ -19,6 +19,8 @@ Files written (npz, float32 unless noted):
     traj.npz         capture (v): two Adam weight steps + one 'full' arch step of the reference loop (loss trajectory)
     loader.npz       loader functions (relation_embedding, semantic_embedding, proc_img_feat, proc_bbox_feat, proc_ques)
     losses.npz       ITM triplet step with BCE_Loss; VGD KLDiv + SmoothL1 loss
+    entry_imports.json  the import surface of the six entry scripts: every `from mmnas... import ...` line as
+                     [line, module, names], and the modules the checkout ships as Cython source only (json, not npz)
 """
 import os
 import sys
@@ -853,7 +855,35 @@ def gen_losses64():
     gen_losses(full64=True, fname='losses64.npz')
 
 
+ENTRY_SCRIPTS = ('search_vqa.py', 'train_vqa.py', 'search_vgd.py', 'train_vgd.py', 'search_itm.py', 'train_itm.py')
+
+
+def gen_entry_imports():
+    """The import surface of the six entry scripts (tests/test_import_surface.py rebuilds a checkout-shaped tree from it):
+    per script every `from mmnas... import a, b` line as [line number, module, [names]]; `cython_only`: the imported
+    modules the checkout ships as a .pyx source without a .py (mmnas/utils/bbox.pyx, built by the checkout's setup.py)."""
+    import json
+    import re
+    out = {'scripts': {}}
+    for s in ENTRY_SCRIPTS:
+        rows = []
+        with open(os.path.join(REF, s)) as f:
+            for ln, line in enumerate(f, 1):
+                m = re.match(r'from (mmnas[\w.]*) import (.+)', line)
+                if m:
+                    rows.append([ln, m.group(1), [n.strip() for n in m.group(2).split(',')]])
+        out['scripts'][s] = rows
+    mods = sorted({r[1] for rows in out['scripts'].values() for r in rows})
+    base = lambda m: os.path.join(REF, *m.split('.'))
+    out['cython_only'] = [m for m in mods if not os.path.exists(base(m) + '.py') and os.path.exists(base(m) + '.pyx')]
+    with open(os.path.join(HERE, 'entry_imports.json'), 'w') as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write('\n')
+    print('entry_imports.json', sum(len(r) for r in out['scripts'].values()), 'import lines')
+
+
 if __name__ == '__main__':
-    which = sys.argv[1:] or ['ops', 'ops_shapes', 'prims', 'mixed', 'nets', 'nets_full', 'traj', 'train_traj', 'loader', 'losses']
+    which = sys.argv[1:] or ['ops', 'ops_shapes', 'prims', 'mixed', 'nets', 'nets_full', 'traj', 'train_traj', 'loader', 'losses',
+                             'entry_imports']
     for w in which:
         globals()['gen_' + w]()

@@ -45,6 +45,8 @@ def _check(d, world, steps=2, warmup=1):
     assert d['n_gpus'] == world and d['steps'] == steps and d['warmup'] == warmup
     assert d['unit'] == 'steps/s' and d['higher_is_better'] is True and d['scaling'] == 'weak' and d['vs_baseline'] is None
     assert d['value'] > 0 and abs(d['value'] - world * 1000.0 / d['ms_per_step']) < 1e-4 * d['value']
+    # the blocks are timed by events inside ONE synchronised window of `steps` steps: the window's wall clock per step agrees
+    assert 0.5 * d['ms_per_step'] < d['wall_ms_per_step'] < 2.0 * d['ms_per_step'] and sum(d['blocks_steps']) == steps
     assert d['final_loss'] == d['final_loss'] and abs(d['final_loss']) < 1e9
     assert d['config']['global_batch'] == 64 * world and d['dtype'].startswith('f32')
     r = d['roofline']
@@ -74,7 +76,7 @@ def test_bench_default_line_is_the_supernet_weight_step_with_sub_records():
     full = os.path.join(ROOT, 'gpurun_out', 'bench_full.json')
     if os.path.exists(full):
         os.remove(full)
-    p = subprocess.run([sys.executable, 'bench.py', '--steps', '6', '--warmup', '1', '--cpu-budget', '3'],
+    p = subprocess.run([sys.executable, 'bench.py', '--steps', '30', '--warmup', '1', '--cpu-budget', '3'],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     assert len(p.stderr.splitlines()) < 20, p.stderr[-3000:]
@@ -93,7 +95,7 @@ def test_bench_default_line_is_the_supernet_weight_step_with_sub_records():
     assert set(line['sub']) == set(d['sub']) and all(s['value'] > 0 and s['ms_per_step'] > 0 for s in line['sub'].values())
     assert [l for l in p.stdout.splitlines() if l.strip()] == [l for l in p.stdout.splitlines() if l.startswith('{')], \
         'stdout must carry the one JSON line and nothing else: ' + p.stdout[-500:]
-    _check(d, 1, steps=6)
+    _check(d, 1, steps=30)
     assert d['metric'].startswith('supernet fwd+bwd steps/sec') and 'WEIGHT step' in d['config']['workload']
     main = {'arch_step', 'bilevel', 'train_vqa'}
     n1 = {'search_vqa_stream', 'search_vqa_dropin', 'search_vqa_dp1', 'train_vqa_dp1'}     # N = 1 only: short records
@@ -105,9 +107,10 @@ def test_bench_default_line_is_the_supernet_weight_step_with_sub_records():
     for r in [d] + [d['sub'][k] for k in main]:
         assert r['value'] > 0 and 0 < r['roofline']['frac'] < 1
         assert r['repeats'] == 5 and r['value_min'] <= r['value'] <= r['value_max']   # median of five timed blocks
+        assert sum(r['blocks_steps']) == r['steps'] and len(r['blocks_ms_per_step']) == 5   # that together make --steps
         cb = r['cpu_baseline']
         assert cb['kind'] == 'port' and cb['value'] > 0 and cb['cores'] >= 1 and cb['unit'] == 'steps/s'
-    assert d['sub']['bilevel']['steps'] == 6
+    assert d['sub']['bilevel']['steps'] == 30
     for k in n1:
         r = d['sub'][k]
         assert r.get('error') is None and r['value'] > 0 and r['host_issue_ms_per_step'] > 0 and r['library_launches_per_step'] > 100, (k, r)
@@ -118,6 +121,42 @@ def test_bench_default_line_is_the_supernet_weight_step_with_sub_records():
     assert d['sub']['search_vqa_stream']['ms_per_step_vs_plain'] < 1.25
     tp = d['roofline']['traffic_pmc']
     assert tp is None or 'source_commit' in tp
+
+
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """--dump-outputs: float32 / float64 arrays under 64 MB -- the loss the line reports, per-parameter gradient norms, the
+    seeded gradient sample, the sampled operators.  The same arguments give the same outputs; so does the same number of
+    steps split differently between warm-up and timed steps (--steps is exactly the timed steps, and nothing runs between the
+    last of them and the dump); one step more gives other outputs."""
+    import numpy as np
+
+    def run(steps, warmup, out):
+        p = subprocess.run([sys.executable, 'bench.py', '--workload', 'search_vqa', '--steps', str(steps), '--warmup', str(warmup),
+                            '--no-cpu-baseline', '--no-fixed-cost', '--full-out', str(out) + '.json',
+                            '--dump-outputs', str(out)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        d = _json_line(p.stdout, str(out) + '.json')
+        assert d['steps'] == steps and sum(d['blocks_steps']) == steps
+        files = sorted(os.listdir(str(out)))
+        assert files == ['grad_norms.npy', 'grad_sample.npy', 'loss.npy', 'sampled_ops.npy'], files
+        got = {f[:-4]: np.load(os.path.join(str(out), f)) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+        assert sum(os.path.getsize(os.path.join(str(out), f)) for f in files) <= 64 << 20
+        assert d['outputs'] == {k: list(a.shape) for k, a in got.items()}
+        assert got['loss'][0] == d['final_loss'] and got['sampled_ops'].shape == (30,)
+        assert got['grad_sample'].size > 1 << 21 and np.isfinite(got['grad_sample']).all() and (got['grad_norms'] > 0).any()
+        return got
+
+    def same(a, b):
+        return (np.array_equal(a['sampled_ops'], b['sampled_ops']) and abs(a['loss'][0] - b['loss'][0]) <= 1e-5 * abs(a['loss'][0])
+                and np.allclose(a['grad_norms'], b['grad_norms'], rtol=1e-4, atol=1e-6 * a['grad_norms'].max())
+                and np.abs(a['grad_sample'] - b['grad_sample']).max() <= 1e-4 * np.abs(a['grad_sample']).max())
+
+    base = tmp_path / 'out'
+    a, b = run(3, 1, str(base) + 'a'), run(3, 1, str(base) + 'b')
+    assert same(a, b)
+    assert same(a, run(2, 2, str(base) + 'c'))             # step 4 of the run either way
+    assert not same(a, run(4, 1, str(base) + 'd'))         # step 5
 
 
 def test_bench_gpus_flag_must_match_the_launch():

@@ -129,3 +129,35 @@ def test_compact_line_keeps_what_limits_the_gemm_class():
     gm = rec['kernel_classes']['gemm']
     assert abs(rl['fixed_cost_share'] - rl['launches_per_step'] * rl['fixed_cost_us_per_launch'] * 1e-3 / gm['ms_per_step']) < 2e-3
     assert json.loads(line)['config']['hip_force_dev_kernarg_source'] in ('set_by_library', 'inherited')
+
+
+def test_timed_blocks_make_exactly_the_requested_steps():
+    """--steps is the number of timed calls in all; --repeats splits them into consecutive blocks of near-equal size."""
+    b = _bench()
+    for calls in range(1, 41):
+        for repeats in range(1, 8):
+            sizes = b.block_sizes(calls, repeats)
+            assert sum(sizes) == calls and len(sizes) == min(repeats, calls) and max(sizes) - min(sizes) <= 1 and min(sizes) >= 1
+
+
+def test_steps_below_one_is_refused():
+    import subprocess
+    import sys
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 2 and '--steps' in p.stderr and not p.stdout
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path):
+    import numpy as np
+    import pytest
+    b = _bench()
+    arrays = {'loss': np.array([1.5]), 'grad_sample': np.arange(10, dtype=np.float32)}
+    b.write_outputs(str(tmp_path / 'o'), arrays)
+    assert sorted(os.listdir(str(tmp_path / 'o'))) == ['grad_sample.npy', 'loss.npy']
+    for k, a in arrays.items():
+        got = np.load(str(tmp_path / 'o' / (k + '.npy')))
+        assert got.dtype == a.dtype and np.array_equal(got, a)
+    with pytest.raises(AssertionError):
+        b.write_outputs(str(tmp_path / 'i'), {'index': np.arange(3)})
+    with pytest.raises(AssertionError):
+        b.write_outputs(str(tmp_path / 'big'), {'x': np.zeros((64 << 20) // 4 + 1, np.float32)})

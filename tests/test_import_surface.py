@@ -1,8 +1,9 @@
 """The drop-in import surface: with this repository on the path next to an integrator's checkout of the
 reference, every `from mmnas... import ...` line of the six entry scripts resolves -- the operator hot path
 (`mmnas.model.*`, `mmnas.utils.{ops_adapter,optimizer,itm_loss}`) to THIS tree, everything else (`mmnas.loader.*`,
-`mmnas.utils.{sampler,vqa,vqaEval,bbox_transform,bbox}`: out of scope) to the checkout.  Child interpreters, because the
-test process itself has `mmnas` imported already."""
+`mmnas.utils.{sampler,vqa,vqaEval,bbox_transform,bbox}`: out of scope) to the checkout.  The checkout is rebuilt in a
+temporary directory from the scripts' recorded import lines (tests/golden/entry_imports.json).  Child interpreters,
+because the test process itself has `mmnas` imported already."""
 import json
 import os
 import subprocess
@@ -11,7 +12,6 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = '/root/reference'
 OURS = {'mmnas.model.hygr_vqa', 'mmnas.model.hygr_vgd', 'mmnas.model.hygr_itm', 'mmnas.model.full_vqa', 'mmnas.model.full_vgd',
         'mmnas.model.full_itm', 'mmnas.model.mixed', 'mmnas.model.modules', 'mmnas.utils.ops_adapter', 'mmnas.utils.optimizer',
         'mmnas.utils.itm_loss'}
@@ -52,23 +52,57 @@ def _resolve(env_extra, cwd, script_dir, scripts):
     return json.loads(p.stdout.strip().splitlines()[-1])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='needs the reference checkout (build container only)')
+def _checkout_tree(co):
+    """A tree shaped like the reference checkout, from the import surface of its six entry scripts
+    (tests/golden/entry_imports.json, written by make_golden.gen_entry_imports): the scripts as their `from mmnas...`
+    lines; every out-of-scope module they import as a stub defining the imported names; the operator modules this tree
+    must shadow as files that raise when imported; the Cython module as its unbuilt .pyx source only."""
+    with open(os.path.join(ROOT, 'tests', 'golden', 'entry_imports.json')) as f:
+        surface = json.load(f)
+    names = {}
+    for rows in surface['scripts'].values():
+        for _, mod, ns in rows:
+            names.setdefault(mod, set()).update(ns)
+    for mod, ns in names.items():
+        path = co.joinpath(*mod.split('.'))
+        path.parent.mkdir(parents=True, exist_ok=True)       # (no __init__.py: the checkout's mmnas is a namespace package)
+        if mod in surface['cython_only']:
+            path.with_suffix('.pyx').write_text('# unbuilt Cython source\n')
+        elif mod in OURS:
+            path.with_suffix('.py').write_text('raise RuntimeError("the checkout\'s %s must be shadowed")\n' % mod)
+        else:
+            path.with_suffix('.py').write_text(''.join('class %s:\n    pass\n' % n for n in sorted(ns)))
+    scripts = []
+    for s, rows in sorted(surface['scripts'].items()):
+        lines = [''] * max(ln for ln, _, _ in rows)          # each import on its line number in the script
+        for ln, mod, ns in rows:
+            lines[ln - 1] = 'from %s import %s' % (mod, ', '.join(ns))
+        (co / s).write_text('\n'.join(lines) + '\n')
+        scripts.append(str(co / s))
+    return scripts, set(surface['cython_only']), sum(len(rows) for rows in surface['scripts'].values())
+
+
 @pytest.mark.parametrize('how', ['script_dir_first', 'pythonpath_pair', 'reference_root_variable'])
 def test_every_mmnas_import_of_the_entry_scripts_resolves_to_the_expected_tree(how, tmp_path):
-    scripts = [os.path.join(REF, n) for n in ('search_vqa.py', 'train_vqa.py', 'search_vgd.py', 'train_vgd.py', 'search_itm.py', 'train_itm.py')]
+    ref = tmp_path / 'checkout'
+    scripts, cython_only, n_lines = _checkout_tree(ref)
+    REF = str(ref)
+    run_dir = tmp_path / 'elsewhere'
+    run_dir.mkdir()
     if how == 'script_dir_first':        # `cd <checkout>; PYTHONPATH=<repo> python3 search_vqa.py`
         got = _resolve({'PYTHONPATH': ROOT}, REF, REF, scripts)
     elif how == 'pythonpath_pair':       # INTEGRATION.md A: PYTHONPATH=<repo>:<checkout>
-        got = _resolve({'PYTHONPATH': ROOT + os.pathsep + REF}, str(tmp_path), '', scripts)
+        got = _resolve({'PYTHONPATH': ROOT + os.pathsep + REF}, str(run_dir), '', scripts)
     else:                                # checkout not on the path at all
-        got = _resolve({'PYTHONPATH': ROOT, 'MMNAS_REFERENCE_ROOT': REF}, str(tmp_path), '', scripts)
-    assert len(got) == 43                # the import lines listed in search_vqa.py:17-24, train_vgd.py:15-21, search_itm.py:17-23, ...
+        got = _resolve({'PYTHONPATH': ROOT, 'MMNAS_REFERENCE_ROOT': REF}, str(run_dir), '', scripts)
+    assert len(got) == n_lines == 43     # the import lines listed in search_vqa.py:17-24, train_vgd.py:15-21, search_itm.py:17-23, ...
     seen_ref = set()
     for key, r in got.items():
         mod = key.split()[-1]
-        if mod == 'mmnas.utils.bbox' and r['origin'] is None:
+        if mod in cython_only:
             # the checkout's Cython module (mmnas/utils/bbox.pyx + setup.py), unbuilt here: the directory it is built
             # into must be on the package's search path
+            assert r['origin'] is None, (key, r)
             assert os.path.join(REF, 'mmnas', 'utils') in r['parent_path'] and os.path.exists(os.path.join(REF, 'mmnas', 'utils', 'bbox.pyx'))
             seen_ref.add(mod)
             continue
@@ -78,11 +112,8 @@ def test_every_mmnas_import_of_the_entry_scripts_resolves_to_the_expected_tree(h
             assert r['import_error'] is None and r['missing'] == [], (key, r)      # e.g. Margin_Loss (search_itm.py:23)
         else:
             assert r['origin'].startswith(REF + os.sep), (key, r['origin'])
+            assert r['import_error'] is None and r['missing'] == [], (key, r)
             seen_ref.add(mod)
-            if r['import_error'] is not None:     # the checkout's own third-party needs (spaCy vectors, Cython build): not ours
-                assert 'mmnas' not in r['import_error'].split(':', 1)[1] or 'bbox' in mod, (key, r['import_error'])
-            else:
-                assert r['missing'] == [], (key, r)
     assert {'mmnas.loader.filepath_vqa', 'mmnas.loader.load_data_vqa', 'mmnas.utils.sampler', 'mmnas.utils.vqa', 'mmnas.utils.vqaEval',
             'mmnas.utils.bbox_transform', 'mmnas.utils.bbox'} <= seen_ref
 

@@ -78,7 +78,14 @@ def test_attflat_mask_lstm():
         assert rel_err(y.detach().numpy(), npz[pre + 'y']) < OTOL
         (y * T(npz[pre + 'g'])).sum().backward()
         assert rel_err(x.grad.numpy(), npz[pre + 'dx']) < 1e-4
+        gscale = max(float(np.max(np.abs(npz[pre + 'g:' + k]))) for k in P)
         for k, p in P.items():
+            if k == 'mlp.linear.bias':
+                # the bias in front of the softmax over the sequence: a softmax is shift-invariant, so its gradient is
+                # exactly zero and both sides hold fp32 round-off (1e-7-class, sign and size depend on the host's
+                # summation order) -- judged as zero against the largest gradient instead of as a relative error
+                assert np.max(np.abs(p.grad.numpy())) < 1e-6 * gscale and np.max(np.abs(npz[pre + 'g:' + k])) < 1e-6 * gscale, k
+                continue
             assert rel_err(p.grad.numpy(), npz[pre + 'g:' + k]) < 1e-4, k
     assert np.array_equal(O.make_mask(T(npz['mask|f'])).numpy(), npz['mask|m'])
     P = {k[len('lstm|P:'):]: T(npz[k]) for k in npz.files if k.startswith('lstm|P:')}

@@ -304,7 +304,7 @@ def test_golden_recipe_regenerates_bit_exact(tmp_path):
     code = ("import sys; sys.path.insert(0, %r)\n"
             "import tests.golden.make_golden as mg\n"
             "mg.HERE = %r\n"
-            "for w in ('prims', 'mixed', 'traj', 'train_traj', 'loader', 'losses', 'nets_full'):\n"
+            "for w in ('prims', 'mixed', 'traj', 'train_traj', 'loader', 'losses', 'nets_full', 'entry_imports'):\n"
             "    getattr(mg, 'gen_' + w)()\n" % (REPO, str(tmp_path)))
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE='1')
     r = subprocess.run([sys.executable, '-c', code], cwd=str(tmp_path), env=env, capture_output=True, text=True,
@@ -316,6 +316,8 @@ def test_golden_recipe_regenerates_bit_exact(tmp_path):
         assert sorted(new.files) == sorted(old.files), w
         for k in new.files:
             assert np.array_equal(new[k], old[k]), (w, k)
+    with open(os.path.join(str(tmp_path), 'entry_imports.json')) as a, open(os.path.join(GOLDEN, 'entry_imports.json')) as b:
+        assert a.read() == b.read()
 
 
 @pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'mmnas')) or os.environ.get('MMNAS_REGEN_FULL64') != '1',

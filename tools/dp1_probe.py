@@ -1,5 +1,5 @@
 import os, sys, time, statistics
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, torch.distributed as dist
 import bench
 from mmnas.model.hygr_vqa import Net_Search
