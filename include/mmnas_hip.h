@@ -453,6 +453,12 @@ typedef struct mmnas_mha_desc {
 
 int mmnas_mha_core_fwd(const mmnas_mha_desc* d, void* stream);
 int mmnas_mha_core_bwd(const mmnas_mha_desc* d, void* stream);
+/* Retrieval scoring (mmnas_amd/retrieval.py): the forward above where query batch b reads the K / V rows and the key-mask row
+ * of batch kv_idx[b] (device int array [B]; every entry must lie inside the K / V / mask arrays -- the caller checks).  Q, O
+ * and lse stay dense [B, ...].  K / V may be strided slices of a wider product (ldk / ldv).  Same arithmetic as
+ * mmnas_mha_core_fwd on gathered K / V / mask: bitwise the same output.  Limits: Sk <= 64, no dropout (drop_p = 0), no
+ * biasT, no q_off / k_off, B <= 65535; anything else returns MMNAS_E_SHAPE / MMNAS_E_ARG. */
+int mmnas_mha_core_fwd_indexed(const mmnas_mha_desc* d, const int* kv_idx, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Operator level: one call = one reference operator forward (or backward).
@@ -714,6 +720,26 @@ int mmnas_adam_step(float* p, const float* g, float* m, float* v, size_t n, floa
                     int step, void* stream);
 /* out[0] += sum of squares of g[0..n) (for clip_grad_norm_). */
 int mmnas_sumsq(const float* g, size_t n, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * ITM retrieval scoring (train_itm.py:437-546 evaluation, :299-363 hard-negative mining; mmnas_amd/retrieval.py).
+ *   mmnas_itm_pair_head: per pair p (one wave each) z = LN(xflat[cap_idx[p]] + yflat[p]) with the LayerNorm of
+ *     modules.py:44-56 (ln_a, ln_b, eps), logit = z . Wp + bp[0] (full_itm.py:109-112); logits[p] = logit (nullable),
+ *     score = sigmoid(logit) into scores[p] -- or, with img_row / cap_col [P] given, into scores[img_row[p] * ld + cap_col[p]].
+ *     xflat [*, D] (indexed by cap_idx), yflat [P, D]; 2 <= D <= 2048.
+ *   mmnas_rank_matrix: S [Ni, Nc] (row stride ld), Nc = G * Ni, caption j belongs to image j / G:
+ *     i2t_rank[i] = #{k : S[i,k] > t_i}, t_i = max_g S[i, G i + g];  i2t_tie[i] = #{k outside i's captions : S[i,k] == t_i};
+ *     t2i_rank[j] = #{i : S[i,j] > S[j/G, j]};                           t2i_tie[j] = #{i != j/G : S[i,j] == S[j/G, j]};
+ *     *nan_flag = 1 if S holds a NaN, else 0.  Every output is overwritten.
+ *   mmnas_row_topk: S [N, C] (row stride ld), C <= 1024, 1 <= k <= C: out[r, 0..k) = the positions of row r's k largest
+ *     scores in descending order, equal scores by the lower position; *nan_flag (nullable) as above.
+ * ------------------------------------------------------------------------------------------ */
+int mmnas_itm_pair_head(const float* xflat, const int* cap_idx, const float* yflat, const float* ln_a, const float* ln_b,
+                        const float* Wp, const float* bp, float* logits, float* scores, const int* img_row, const int* cap_col,
+                        long ld, int P, int D, float eps, void* stream);
+int mmnas_rank_matrix(const float* S, int Ni, int Nc, long ld, int* i2t_rank, int* i2t_tie, int* t2i_rank, int* t2i_tie,
+                      int* nan_flag, void* stream);
+int mmnas_row_topk(const float* S, int N, int C, long ld, int k, int* out, int* nan_flag, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Measurement aid (bench.py roofline): while enabled, every kernel launch of the classes below is

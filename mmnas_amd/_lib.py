@@ -213,6 +213,10 @@ SYMBOLS = {
     'mmnas_set_rel_overlap': (_i, [_i]),
     'mmnas_mha_core_fwd': (_i, [C.POINTER(MhaDesc), _fp]),
     'mmnas_mha_core_bwd': (_i, [C.POINTER(MhaDesc), _fp]),
+    'mmnas_mha_core_fwd_indexed': (_i, [C.POINTER(MhaDesc), _fp, _fp]),
+    'mmnas_itm_pair_head': (_i, [_fp] * 11 + [C.c_long, _i, _i, _f, _fp]),
+    'mmnas_rank_matrix': (_i, [_fp, _i, _i, C.c_long, _fp, _fp, _fp, _fp, _fp, _fp]),
+    'mmnas_row_topk': (_i, [_fp, _i, _i, C.c_long, _i, _fp, _fp, _fp]),
     'mmnas_att_op_plan': (_i, [C.POINTER(AttOp), C.POINTER(Plan)]),
     'mmnas_att_op_fwd': (_i, [C.POINTER(AttOp), _fp]),
     'mmnas_att_op_bwd': (_i, [C.POINTER(AttOp), _fp]),

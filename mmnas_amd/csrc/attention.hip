@@ -101,8 +101,10 @@ __device__ __forceinline__ void load_tiles2(float* __restrict__ da, const float*
 #ifndef MMNAS_DBG_FWD
 #define MMNAS_DBG_FWD 0   // timing experiments only (wrong results): bit mask of forward phases left out (tools/mha_fwd_phases.sh)
 #endif
-template <int DHC, int NKC, int NW>
-__device__ __forceinline__ void mha_fwd_body(const MhaK& p, const int qblk) {
+// IDX (retrieval scoring, mmnas_mha_core_fwd_indexed): query batch b reads the K / V rows and key mask of batch kvidx[b]; Q and O
+// stay dense.  A compile-time variant: the IDX = false instantiations are the kernels they were before it existed.
+template <int DHC, int NKC, int NW, bool IDX = false>
+__device__ __forceinline__ void mha_fwd_body(const MhaK& p, const int qblk, const int* __restrict__ kvidx = nullptr) {
   constexpr int LD = DHC + 4, NT = 64 * NW, JC = DHC >= 32 ? DHC / 32 : 1;
   __shared__ __attribute__((aligned(16))) float Qs[32 * NW * LD];
   __shared__ __attribute__((aligned(16))) float KVs[32 * NKC * LD];
@@ -110,7 +112,8 @@ __device__ __forceinline__ void mha_fwd_body(const MhaK& p, const int qblk) {
   const int b = blockIdx.z, h = blockIdx.y, q0 = qblk * 32 * NW;
   const int SqS = p.Sq, SkS = p.Sk;   // strides of the per-(batch, head) arrays; the lengths of this batch element:
   int Sq = p.Sq, Sk = p.Sk;
-  size_t qrow0 = (size_t)b * p.Sq, krow0 = (size_t)b * p.Sk;
+  const int kb = IDX ? kvidx[b] : b;   // batch of the key / value rows and of the key mask
+  size_t qrow0 = (size_t)b * p.Sq, krow0 = (size_t)kb * p.Sk;
   if (p.qoff) { const int o = p.qoff[b]; Sq = p.qoff[b + 1] - o; qrow0 = (size_t)o; }
   if (p.koff) { const int o = p.koff[b]; Sk = p.koff[b + 1] - o; krow0 = (size_t)o; }
   if (q0 >= Sq || Sk <= 0) return;   // (packed rows: this query block lies behind the sequence's end; workgroup-uniform)
@@ -126,7 +129,7 @@ __device__ __forceinline__ void mha_fwd_body(const MhaK& p, const int qblk) {
   for (int j = 0; j < NMW; ++j) {
     const int key = 64 * j + lane;
     const bool inr = key < Sk;
-    const bool mk = p.mask && inr && p.mask[(size_t)b * SkS + (inr ? key : 0)];
+    const bool mk = p.mask && inr && p.mask[(size_t)kb * SkS + (inr ? key : 0)];
     mbits[j] = __ballot(mk) >> (4 * hh);
     vbits[j] = __ballot(inr) >> (4 * hh);
   }
@@ -303,6 +306,12 @@ __device__ __forceinline__ void mha_fwd_body(const MhaK& p, const int qblk) {
 template <int DHC, int NKC, int NW>
 __global__ void __launch_bounds__(64 * NW, (NKC <= 4 && NW == 4) ? 2 : 1) mha_fwd_kernel(const MhaK p) {
   mha_fwd_body<DHC, NKC, NW>(p, blockIdx.x);
+}
+
+// Retrieval scoring: the guided operators' cores over a per-caption K / V cache (see mha_fwd_body).
+template <int DHC, int NKC, int NW>
+__global__ void __launch_bounds__(64 * NW, (NKC <= 4 && NW == 4) ? 2 : 1) mha_fwd_idx_kernel(const MhaK p, const int* kvidx) {
+  mha_fwd_body<DHC, NKC, NW, true>(p, blockIdx.x, kvidx);
 }
 
 // Two attention cores of one geometry in ONE launch (the self / relation-self candidates of a supernet decoder node in the
@@ -1070,6 +1079,38 @@ int mha_core_fwd_pair(const mmnas_mha_desc* d0, const mmnas_mha_desc* d1, hipStr
   const int nqb = cdiv(k0.Sq, 128);
   MMNAS_LAUNCH((mha_fwd_pair_kernel<64, 4, 4>), dim3(2 * nqb, k0.H, k0.B), dim3(256), 0, st, k0, k1, nqb);
   return check_launch("mha_core_fwd_pair");
+}
+
+template <int DHC>
+static void launch_fwd_idx(const MhaK& k, const int* kv_idx, hipStream_t st) {
+  const int nkc = cdiv(k.Sk, 32);
+#define FWDI(NKC, NW) MMNAS_LAUNCH((mha_fwd_idx_kernel<DHC, NKC, NW>), dim3(cdiv(k.Sq, 32 * NW), k.H, k.B), \
+                                   dim3(64 * NW), 0, st, k, kv_idx)
+  // (the geometry choice of launch_fwd for <= 64 keys: the same instantiation shapes, hence the same per-query arithmetic)
+  const int nwmax = mha_nw();
+  if (k.Sq <= 32) { if (nkc <= 1) FWDI(1, 1); else FWDI(2, 1); }
+  else if (k.Sq <= 64 || nwmax == 2) { if (nkc <= 1) FWDI(1, 2); else FWDI(2, 2); }
+  else { if (nkc <= 1) FWDI(1, 4); else FWDI(2, 4); }
+#undef FWDI
+}
+
+// retrieval.hip: mmnas_mha_core_fwd_indexed (the forward of mmnas_mha_core_fwd with the K / V / mask batch taken from kv_idx)
+int mha_core_fwd_indexed(const mmnas_mha_desc* d, const int* kv_idx, hipStream_t st) {
+  MhaK k;
+  int rc = fill(d, k, false);
+  if (rc) return rc;
+  MMNAS_REQUIRE(kv_idx, MMNAS_E_ARG, "mha_indexed: null kv_idx");
+  MMNAS_REQUIRE(d->Sk <= 64, MMNAS_E_SHAPE, "mha_indexed: Sk=%d keys; the indexed core serves at most 64 keys", d->Sk);
+  MMNAS_REQUIRE(d->B <= 65535, MMNAS_E_SHAPE, "mha_indexed: B=%d query batches; at most 65535 per call", d->B);
+  MMNAS_REQUIRE(d->drop_p == 0.f, MMNAS_E_ARG, "mha_indexed: drop_p=%g; the indexed core has no dropout", d->drop_p);
+  MMNAS_REQUIRE(!d->biasT, MMNAS_E_ARG, "mha_indexed: the indexed core has no score bias (biasT must be NULL)");
+  MMNAS_REQUIRE(!d->q_off && !d->k_off, MMNAS_E_ARG, "mha_indexed: the indexed core has no packed rows (q_off / k_off must be NULL)");
+  const double bhqk = (double)k.B * k.H * k.Sq * k.Sk;
+  ProfScope ps(MMNAS_K_MHA_FWD, 4.0 * bhqk * k.dh, 4.0 * ((double)k.B * k.H * k.dh * (2.0 * k.Sq + 2.0 * k.Sk)), st);
+  if (k.dh >= 64) { k.nch = k.dh / 64; launch_fwd_idx<64>(k, kv_idx, st); }
+  else if (k.dh == 32) { k.nch = 1; launch_fwd_idx<32>(k, kv_idx, st); }
+  else { k.nch = 1; launch_fwd_idx<16>(k, kv_idx, st); }
+  return check_launch("mha_core_fwd_indexed");
 }
 
 }  // namespace mmnas
