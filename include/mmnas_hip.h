@@ -742,6 +742,27 @@ int mmnas_rank_matrix(const float* S, int Ni, int Nc, long ld, int* i2t_rank, in
 int mmnas_row_topk(const float* S, int N, int C, long ld, int k, int* out, int* nan_flag, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Visual grounding targets and evaluation (configs[3], train_vgd; mmnas_amd/grounding.py).  One wave per sample.
+ * Errors found on the device are OR-ed into *err_flag (never cleared here): 1 = a NaN / infinite input, 2 = nobj outside 1..S
+ * (that sample's outputs are then all zero).  Host-side: B >= 0, 1 <= S <= 1024, non-null pointers, else MMNAS_E_SHAPE / _ARG.
+ *   mmnas_vgd_targets: the loader's proc_bbox_label (load_data_vgd.py:240-282, get_sigmoid_score :228-237) for a batch:
+ *     proposals bbox [B,S,4] f32 (x1,y1,x2,y2), nobj [B], ground truth gt [B,4] f64; IoU as overlaps.py bbox_overlaps (f64);
+ *     mode 0 = kld: score = f32(IoU) / (float32 pairwise sum + 1e-8) over the rows with IoU >= thr, mode 1 = bce: 0.8 / 0.9 / 1
+ *     stepped at 0.6 / 0.7; regression targets as bbox_transform.py:10-27 (proposal side f32, the rest f64), then
+ *     (t - mean) / std in f64 when norm (host array mean[4], std[4]; nullable), rounded to f32 once.  Outputs scores [B,S],
+ *     scores_mask [B] (max IoU >= thr), transformed [B,S,4], bbox_mask [B,S]; rows >= nobj[b] are zero in every output.
+ *   mmnas_vgd_ground: one evaluation batch of train_vgd.py:436-453: idx[b] = argmax of pred_scores[b, 0..S) (padded rows
+ *     included; ties: the lowest index), that row decoded by bbox_transform_inv (bbox_transform.py:29-63, f32) from
+ *     bbox / pred_reg, clipped to (w - 1, h - 1) of img_shape [B,2] = (h, w) (clip_boxes :65-78) into box[b], iou[b] = its f64
+ *     IoU with gt [B,4] f32, hit[b] = iou >= thr; counts (nullable, int64 [2]) += (hits, samples).
+ * ------------------------------------------------------------------------------------------ */
+int mmnas_vgd_targets(const float* bbox, const int* nobj, const double* gt, int B, int S, double thr, int mode, const double* norm,
+                      float* scores, float* scores_mask, float* transformed, float* bbox_mask, int* err_flag, void* stream);
+int mmnas_vgd_ground(const float* pred_scores, const float* pred_reg, const float* bbox, const float* img_shape, const float* gt,
+                     int B, int S, double thr, long long* idx, float* box, double* iou, unsigned char* hit, long long* counts,
+                     int* err_flag, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement aid (bench.py roofline): while enabled, every kernel launch of the classes below is
  * bracketed by HIP events recorded on the stream it is launched on and tagged with its ALGORITHMIC
  * flops / bytes; mmnas_prof_collect() synchronises the events, sums per class and resets.

@@ -217,6 +217,8 @@ SYMBOLS = {
     'mmnas_itm_pair_head': (_i, [_fp] * 11 + [C.c_long, _i, _i, _f, _fp]),
     'mmnas_rank_matrix': (_i, [_fp, _i, _i, C.c_long, _fp, _fp, _fp, _fp, _fp, _fp]),
     'mmnas_row_topk': (_i, [_fp, _i, _i, C.c_long, _i, _fp, _fp, _fp]),
+    'mmnas_vgd_targets': (_i, [_fp, _fp, _fp, _i, _i, C.c_double, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    'mmnas_vgd_ground': (_i, [_fp] * 5 + [_i, _i, C.c_double] + [_fp] * 7),
     'mmnas_att_op_plan': (_i, [C.POINTER(AttOp), C.POINTER(Plan)]),
     'mmnas_att_op_fwd': (_i, [C.POINTER(AttOp), _fp]),
     'mmnas_att_op_bwd': (_i, [C.POINTER(AttOp), _fp]),
