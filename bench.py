@@ -1,11 +1,14 @@
 """Benchmark of the candidate-operator hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload all|search_vqa|arch_vqa|bilevel_vqa|train_vqa]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload all|search_vqa|arch_vqa|bilevel_vqa|train_vqa] [--full]
 
 Headline (BASELINE.json `metric`: supernet fwd+bwd steps/sec, VQA, bs=64 per GPU): the supernet WEIGHT step of
 search_vqa.py:279-292 -- sample an architecture, forward, BCE(sum), backward, gradient exchange -- on Net_Search with
 HSIZE 256, 100x2048 region features + 14 tokens, dropout 0.1, one synthetic batch of 64 per GPU resident in HBM.
-With the default `--workload all` the same process then times, each for K steps of its own, and reports under "sub":
+A plain run does only what the headline needs: set up, warm up, time the K steps, write --dump-outputs, print the line.
+Everything else below -- sub records, the empty-queue host time, the roofline pass and its fixed-cost microbenchmark,
+the CPU baselines, the side file -- runs only with `--full`.
+With `--full` and the default `--workload all` the same process then times, each for K steps of its own, and reports under "sub":
     arch_step  the architecture step, MODE 'full' (search_vqa.py:317-331): forward of all 96 candidates, backward
                through the 30 sampled ones, alpha-gate gradient exchange
     bilevel    one round of the bilevel loop (search_vqa.py:149-150): 5 weight steps WITH clip + Adam and 1 arch
@@ -33,17 +36,19 @@ and cut into `--repeats` blocks of consecutive steps by HIP events (default 5; a
 loss, every parameter's gradient (norms, and a fixed seeded sample of the elements), the sampled operators -- is
 written as DIR/<name>.npy (float32 / float64, < 64 MB).  Inputs, weights and samplers are seeded: the same arguments
 give the same inputs on every run, so two builds can be compared output for output.
-Every record carries its own `roofline` (the fp32-MFMA GEMM kernel class, the dominant kernel, measured with HIP
-events on the launch stream over a repeat of the timed steps right after the timed region -- the events cost ~9 % of a
-step, so they stay out of the throughput measurement) and, at N = 1, its own `cpu_baseline` (the CPU oracle, a port of
-the reference step, timed on this box's host cores on the same weights and batch).
+With `--full` every record carries its own `roofline` (the fp32-MFMA GEMM kernel class, the dominant kernel, measured
+with HIP events on the launch stream over a repeat of the timed steps right after the timed region -- the events cost
+~9 % of a step, so they stay out of the throughput measurement) and, at N = 1, its own `cpu_baseline` (the CPU oracle,
+a port of the reference step, timed on this box's host cores on the same weights and batch).  None of it runs before
+the headline's timed steps, so `--full` changes neither the headline's time nor its dumped outputs.
 
 N > 1: launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (one rank per GPU,
 RCCL).  Every rank runs its own batch (weak scaling), gradients are averaged inside the step, time is the max over
 ranks.  `--gpus N` without a launcher (WORLD_SIZE unset) spawns the N ranks itself before anything touches the GPU;
 a WORLD_SIZE that disagrees with --gpus is an error.  Rank 0 prints ONE compact JSON line (< 8000
 characters: the contract's fields + roofline + cpu_baseline + one short object per sub record) as the last line of stdout;
-the full records (kernel classes, per-block times, PMC detail, notes) go to gpurun_out/bench_full.json (--full-out).
+with `--full` the full records (kernel classes, per-block times, PMC detail, notes) go to the side file bench_full.json
+in the repository root (--full-out names another, and implies --full).
 """
 import argparse
 import json
@@ -453,7 +458,11 @@ def main():
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--workload', default='all', choices=['all'] + list(WORKLOADS),
-                    help='all = search_vqa (headline) + arch_vqa + bilevel_vqa + train_vqa; train_vgd / train_itm run by name only')
+                    help='all = search_vqa (headline), with --full + arch_vqa + bilevel_vqa + train_vqa (+ the N = 1 records); '
+                         'train_vgd / train_itm run by name only')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: sub records, empty-queue host time, roofline pass, '
+                         'CPU baselines, side file')
     ap.add_argument('--batch', type=int, default=B_DEFAULT)
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-budget', type=float, default=20.0, help='seconds of CPU work per cpu_baseline record')
@@ -464,7 +473,8 @@ def main():
                          'flavour BASELINE configs[4] names ("fp16 MFMA"; --workload train_itm only, never a headline); the JSON '
                          'line says which in dtype and config')
     ap.add_argument('--no-prof', action='store_true', help='skip the roofline pass (per-launch HIP events)')
-    ap.add_argument('--full-out', default=None, help='where the full record goes (default gpurun_out/bench_full.json)')
+    ap.add_argument('--full-out', default=None, help='where the full record goes (implies --full; default bench_full.json in the '
+                                                     'repository root)')
     ap.add_argument('--no-fixed-cost', action='store_true', help='skip the per-launch fixed-cost microbenchmark behind roofline.fixed_cost_share '
                     '(~1900 extra GEMM launches: keep them out of a kernel trace of the steps)')
     ap.add_argument('--repeats', type=int, default=5, help='blocks the --steps timed steps are split into; value = the median block')
@@ -474,6 +484,7 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.repeats < 1:
         ap.error('--steps and --repeats must be at least 1')
+    args.full = args.full or args.full_out is not None
 
     env_world = os.environ.get('WORLD_SIZE')
     if env_world is None and args.gpus > 1:
@@ -555,7 +566,12 @@ def main():
     init = {'token_size': VOCAB, 'ans_size': ANS, 'pretrained_emb': emb}
     from mmnas_amd.harness import fused_loss
     loss_fn = fused_loss(torch.nn.BCEWithLogitsLoss(reduction='sum'))
-    wanted = [w for w in WORKLOADS if w not in EXTRA and (w not in N1_SUBS or world == 1)] if args.workload == 'all' else [args.workload]
+    if args.workload != 'all':
+        wanted = [args.workload]
+    elif args.full:
+        wanted = [w for w in WORKLOADS if w not in EXTRA and (w not in N1_SUBS or world == 1)]
+    else:
+        wanted = ['search_vqa']
     if world > 1 and any(w in N1_SUBS for w in wanted):
         sys.stderr.write('bench.py: %s is an N = 1 record\n' % wanted[0])
         sys.exit(2)
@@ -968,21 +984,23 @@ def main():
         # host time of ONE call issued into an EMPTY queue (synchronise first): in the timed blocks the host runs ahead
         # until the launch queue is full and then waits on it, so there `host_issue` approaches the GPU time of a
         # GPU-bound step; this is what the host itself needs
-        host_alone = []
-        for _ in range(3):
+        host_alone_ms = None
+        if args.full:
+            host_alone = []
+            for _ in range(3):
+                barrier()
+                th = time.perf_counter()
+                step()
+                host_alone.append(time.perf_counter() - th)
             barrier()
-            th = time.perf_counter()
-            step()
-            host_alone.append(time.perf_counter() - th)
-        barrier()
-        host_alone_ms = 1000.0 * sorted(host_alone)[1] / per_call
+            host_alone_ms = 1000.0 * sorted(host_alone)[1] / per_call
         # Roofline pass: the same steps repeated right after the timed region with every library launch carrying a
         # start/stop HIP event (on the launch stream).  Kept out of the timed region because the events themselves
         # cost ~9 % of the step (a completion signal per dispatch); launches, shapes and data are identical.
         stats = None
         prof_calls = min(calls, max(1, (4 if (wl in N1_SUBS and not wl.endswith('_unpad')) else 10) // per_call))
         prof_elapsed = 0.0
-        if not args.no_prof:
+        if args.full and not args.no_prof:
             L.check(lib.mmnas_prof_enable(1))
             tp = time.perf_counter()
             for _ in range(prof_calls):
@@ -1010,8 +1028,9 @@ def main():
             'step_frac_of_mfma_peak': flops_pp / spp / 1e12 / PEAK_MFMA_F32_TFLOPS,
             'final_loss': float(loss.detach()),
             'host_issue_ms_per_step': 1000.0 * enq_pp,
-            'host_issue_ms_per_step_empty_queue': host_alone_ms,
         }
+        if host_alone_ms is not None:
+            rec['host_issue_ms_per_step_empty_queue'] = host_alone_ms
         if outputs is not None:
             rec['outputs'] = {k: list(v.shape) for k, v in outputs.items()}
         if world > 1:
@@ -1118,7 +1137,7 @@ def main():
         recs['search_vqa_dropin']['harness_bilevel_ms_per_step'] = recs['bilevel_vqa']['ms_per_step']
 
     # ---- CPU baselines (rank 0, N = 1 only) ----
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         threads = cpu_threads()
         t_w = t_a = None
         if any(w in recs for w in ('search_vqa', 'arch_vqa', 'bilevel_vqa')):
@@ -1187,14 +1206,16 @@ def main():
             out['sub'] = sub
         # The driver keeps ~16 KB of stdout: the LINE is the compact record (headline + config + roofline + cpu_baseline +
         # one short object per sub record); everything measured goes to the side file the line names.
-        full_path = args.full_out or os.path.join(REPO, 'gpurun_out', 'bench_full.json')
-        try:
-            os.makedirs(os.path.dirname(full_path), exist_ok=True)
-            with open(full_path, 'w') as f:
-                json.dump(out, f, indent=1)
-            full_ref = os.path.relpath(full_path, REPO)
-        except OSError as e:
-            full_ref = 'not written: %s' % e
+        full_ref = None
+        if args.full:
+            full_path = args.full_out or os.path.join(REPO, 'bench_full.json')
+            try:
+                os.makedirs(os.path.dirname(os.path.abspath(full_path)), exist_ok=True)
+                with open(full_path, 'w') as f:
+                    json.dump(out, f, indent=1)
+                full_ref = os.path.relpath(full_path, REPO)
+            except OSError as e:
+                full_ref = 'not written: %s' % e
         line = fit_line(compact_line(out, full_ref))
     if world > 1 or state.get('own_group'):
         dist.destroy_process_group()

@@ -68,21 +68,21 @@ def test_bench_single_gpu(workload, tmp_path):
 
 
 def test_bench_default_line_is_the_supernet_weight_step_with_sub_records():
-    """The driver's command (no --workload): headline = the BASELINE metric's workload, the other three under `sub`,
+    """The --full command without --workload: headline = the BASELINE metric's workload, the other three under `sub`,
     every record with its own roofline and CPU baseline -- in the side file; the LINE stays under 8000 characters with
     `roofline`, `cpu_baseline` and one short object per sub record, and stderr stays quiet."""
     env = dict(os.environ, NCCL_DEBUG='VERSION')   # (RCCL would print a version banner to stdout from the one-rank records)
     env.pop('HIP_FORCE_DEV_KERNARG', None)         # bench.py sets it itself and records it
-    full = os.path.join(ROOT, 'gpurun_out', 'bench_full.json')
+    full = os.path.join(ROOT, 'bench_full.json')
     if os.path.exists(full):
         os.remove(full)
-    p = subprocess.run([sys.executable, 'bench.py', '--steps', '30', '--warmup', '1', '--cpu-budget', '3'],
+    p = subprocess.run([sys.executable, 'bench.py', '--full', '--steps', '30', '--warmup', '1', '--cpu-budget', '3'],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     assert len(p.stderr.splitlines()) < 20, p.stderr[-3000:]
     d = _json_line(p.stdout, full)
     line = d['_line']
-    assert line['full_record'] == 'gpurun_out/bench_full.json' and line['config']['hip_force_dev_kernarg'] == '1'
+    assert line['full_record'] == 'bench_full.json' and line['config']['hip_force_dev_kernarg'] == '1'
     assert 'NCCL_DEBUG' not in line['config']['rccl_env']
     assert line['cpu_baseline']['kind'] == 'port' and line['cpu_baseline']['value'] > 0 and 0 < line['roofline']['frac'] < 1
     # round 6 (VERDICT r5 item 8): what LIMITS the d = 256 GEMM class is in the line -- the measured share of per-launch fixed
@@ -123,6 +123,53 @@ def test_bench_default_line_is_the_supernet_weight_step_with_sub_records():
     assert tp is None or 'source_commit' in tp
 
 
+def _same_outputs(a, b):
+    """Two --dump-outputs of the same steps: the same sampled operators, loss and gradients up to run-to-run round-off."""
+    import numpy as np
+    return (np.array_equal(a['sampled_ops'], b['sampled_ops']) and abs(a['loss'][0] - b['loss'][0]) <= 1e-5 * abs(a['loss'][0])
+            and np.allclose(a['grad_norms'], b['grad_norms'], rtol=1e-4, atol=1e-6 * a['grad_norms'].max())
+            and np.abs(a['grad_sample'] - b['grad_sample']).max() <= 1e-4 * np.abs(a['grad_sample']).max())
+
+
+def _load_outputs(out):
+    import numpy as np
+    return {f[:-4]: np.load(os.path.join(out, f)) for f in sorted(os.listdir(out))}
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """The plain command (no --full) does only what the headline needs: one JSON line with the contract's fields for the
+    supernet weight step alone -- no sub records, empty-queue host time, roofline pass or CPU baseline, and no side file --
+    and its timed steps compute what the same steps of a --full run compute."""
+    side = os.path.join(ROOT, 'bench_full.json')
+    if os.path.exists(side):
+        os.remove(side)
+    plain = str(tmp_path / 'plain')
+    p = subprocess.run([sys.executable, 'bench.py', '--gpus', '1', '--steps', '3', '--warmup', '1', '--dump-outputs', plain],
+                       cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1 and lines[0].startswith('{'), p.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d['n_gpus'] == 1 and d['steps'] == 3 and d['warmup'] == 1 and d['repeats'] == 3
+    assert d['unit'] == 'steps/s' and d['higher_is_better'] is True and d['scaling'] == 'weak' and d['vs_baseline'] is None
+    assert d['value'] > 0 and abs(d['value'] - 1000.0 / d['ms_per_step']) < 1e-4 * d['value']
+    assert d['value_min'] <= d['value'] <= d['value_max'] and d['final_loss'] == d['final_loss']
+    assert d['metric'].startswith('supernet fwd+bwd steps/sec') and 'WEIGHT step' in d['config']['workload']
+    assert 'bf16x6' in d['dtype'] and d['config']['global_batch'] == 64 and d['full_record'] is None
+    for k in ('sub', 'roofline', 'hbm_kernels', 'kernel_ms_per_step', 'cpu_baseline', 'gpu_vs_cpu', 'host_issue_ms_per_step_empty_queue'):
+        assert k not in d, k
+    assert not os.path.exists(side)
+    got = _load_outputs(plain)
+    assert sorted(got) == ['grad_norms', 'grad_sample', 'loss', 'sampled_ops']
+    assert abs(got['loss'][0] - d['final_loss']) <= 1e-6 * abs(d['final_loss'])
+    full = str(tmp_path / 'full')
+    p = subprocess.run([sys.executable, 'bench.py', '--full', '--workload', 'search_vqa', '--steps', '3', '--warmup', '1',
+                        '--no-cpu-baseline', '--no-fixed-cost', '--full-out', full + '.json', '--dump-outputs', full],
+                       cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    assert _same_outputs(got, _load_outputs(full))
+
+
 def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
     """--dump-outputs: float32 / float64 arrays under 64 MB -- the loss the line reports, per-parameter gradient norms, the
     seeded gradient sample, the sampled operators.  The same arguments give the same outputs; so does the same number of
@@ -147,16 +194,11 @@ def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
         assert got['grad_sample'].size > 1 << 21 and np.isfinite(got['grad_sample']).all() and (got['grad_norms'] > 0).any()
         return got
 
-    def same(a, b):
-        return (np.array_equal(a['sampled_ops'], b['sampled_ops']) and abs(a['loss'][0] - b['loss'][0]) <= 1e-5 * abs(a['loss'][0])
-                and np.allclose(a['grad_norms'], b['grad_norms'], rtol=1e-4, atol=1e-6 * a['grad_norms'].max())
-                and np.abs(a['grad_sample'] - b['grad_sample']).max() <= 1e-4 * np.abs(a['grad_sample']).max())
-
     base = tmp_path / 'out'
     a, b = run(3, 1, str(base) + 'a'), run(3, 1, str(base) + 'b')
-    assert same(a, b)
-    assert same(a, run(2, 2, str(base) + 'c'))             # step 4 of the run either way
-    assert not same(a, run(4, 1, str(base) + 'd'))         # step 5
+    assert _same_outputs(a, b)
+    assert _same_outputs(a, run(2, 2, str(base) + 'c'))             # step 4 of the run either way
+    assert not _same_outputs(a, run(4, 1, str(base) + 'd'))         # step 5
 
 
 def test_bench_gpus_flag_must_match_the_launch():

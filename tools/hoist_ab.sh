@@ -4,7 +4,7 @@
 #   MMNAS_GUIDED_HOIST the key / value projections of all guided operators as grouped launches
 # bash tools/hoist_ab.sh > profiles/r05_hoist_ab.txt      (each line: median ms per step of 5 blocks of 20 steps)
 one() {  # workload rel guided
-  MMNAS_REL_HOIST=$2 MMNAS_GUIDED_HOIST=$3 python3 bench.py --workload $1 --no-cpu-baseline 2>/dev/null | python3 -c "
+  MMNAS_REL_HOIST=$2 MMNAS_GUIDED_HOIST=$3 python3 bench.py --full --workload $1 --no-cpu-baseline 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 k = d.get('kernel_ms_per_step', {})

@@ -1,7 +1,7 @@
 """Aggregate a MMNAS_PROF_DUMP file (one row per bracketed launch: kind,tag,ms,flops,bytes) by tag.
 
-    MMNAS_PROF_DUMP=gpurun_out/shapes.csv python bench.py --steps 5 --no-cpu-baseline
-    python tools/prof_shapes.py gpurun_out/shapes.csv 5
+    MMNAS_PROF_DUMP=shapes.csv python bench.py --full --steps 5 --no-cpu-baseline    (the roofline pass writes the rows)
+    python tools/prof_shapes.py shapes.csv 5
 """
 import collections
 import sys

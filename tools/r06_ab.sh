@@ -4,7 +4,7 @@
 #   MMNAS_DP_TAIL_MAIN  end of the data-parallel step on the backward's own stream + one scatter launch (dp.py)
 # bash tools/r06_ab.sh > profiles/r06_ab.txt
 one() {  # workload ENV=VALUE
-  env $2 python3 bench.py --workload $1 --no-cpu-baseline 2>/dev/null | python3 -c "
+  env $2 python3 bench.py --full --workload $1 --no-cpu-baseline 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 k = d.get('kernel_ms_per_step', {})

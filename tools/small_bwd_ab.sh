@@ -2,7 +2,7 @@
 # A/B of the short-sequence backward (small.hip: sa_small_bwd_kernel, MMNAS_SMALL_BWD) on ONE box, alternating runs.
 # bash tools/small_bwd_ab.sh > profiles/r05_small_bwd_ab.txt   (each line: median ms per step of 5 blocks of 20 steps)
 one() {  # workload small_bwd
-  MMNAS_SMALL_BWD=$2 python3 bench.py --workload $1 --no-cpu-baseline 2>/dev/null | python3 -c "
+  MMNAS_SMALL_BWD=$2 python3 bench.py --full --workload $1 --no-cpu-baseline 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 k = d.get('kernel_ms_per_step', {})

@@ -2,7 +2,7 @@
 # A/B of the one-launch FeedForward forward for short row counts (small.hip: ffn_small_fwd_kernel, MMNAS_SMALL_FFN) on ONE box.
 # bash tools/small_ffn_ab.sh > profiles/r05_small_ffn_ab.txt   (each line: median ms per step of 5 blocks of 20 steps)
 one() {  # workload small_ffn
-  MMNAS_SMALL_FFN=$2 python3 bench.py --workload $1 --no-cpu-baseline 2>/dev/null | python3 -c "
+  MMNAS_SMALL_FFN=$2 python3 bench.py --full --workload $1 --no-cpu-baseline 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 k = d.get('kernel_ms_per_step', {})
