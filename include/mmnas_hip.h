@@ -763,6 +763,34 @@ int mmnas_vgd_ground(const float* pred_scores, const float* pred_reg, const floa
                      int* err_flag, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * VQA answer accuracy and soft answer targets (configs[0] / [1], search_vqa / train_vqa; mmnas_amd/answering.py).
+ * Errors found on the device are OR-ed into *err_flag (never cleared here): 1 = a NaN logit, 2 = an index out of range.
+ * The credit table (AnswerCredit, built on the host) is CSR over nq questions: row_ptr [nq+1], col [*] vocabulary index,
+ * k [*] = sum over the question's n answers of min(3, #other matching answers), i.e. VQAEval's accuracy (vqaEval.py:68-120)
+ * times 3n; only k > 0 is stored, each row's columns distinct.
+ *   mmnas_vqa_answer: one evaluation batch of train_vqa.py:379-393 and its credit.  Row b of logits [B, A] (row stride ld >= A)
+ *     goes to slot s = slot_idx[b] (nullable; else slot_base + slot_step * b); s == -1 skips the row, s >= nslots skips it
+ *     too (the sampler's padding) but is an index error when slot_idx is given; s < -1 skips it with an index error.  pred[s] = argmax of the row (int64; np.argmax:
+ *     the lowest index of the maximum, infinities ordinary values, a NaN above every number -> flag 1).  With credit (nullable;
+ *     then row_ptr, col and k are required): q = qmap[s] (nullable: q = s); credit[s] = k(q, pred[s]) (0 when not stored),
+ *     -1 when q == -1 or q is outside -1..nq-1 (flag 2).  count (nullable) [nslots]: count[s] += 1.  One wave per row.
+ *   mmnas_vqa_accuracy: for p < N, q = qmap[p] (nullable: q = p): totals (int64, zeroed by the caller) [2 n_at + 2 n_qt] +=
+ *     (sum of credit[p], count) by ans_type[q], then by ques_type[q] (the layout: at sums, at counts, qt sums, qt counts).
+ *     A q, type or negative credit out of range is skipped with flag 2.  1 <= n_at, n_qt <= 256, N <= 2^28.  Exact integers:
+ *     LDS histograms per workgroup, 64-bit global atomics.
+ *   mmnas_vqa_answer_targets: the loader's proc_ans / get_score (load_data_vqa.py:299-333) from answer indices: ans_ix [B, n]
+ *     (-1 = not in the vocabulary; outside -1..A-1: flag 2, ignored), out [B, A] float32 = 0 / .3 / .6 / .9 / 1 by how often
+ *     the column occurs in the row (every element written).  1 <= n <= 64.  One wave per row.
+ * Host-side: negative sizes, ld < A, a type count or n out of range and null pointers return MMNAS_E_SHAPE / _ARG.
+ * ------------------------------------------------------------------------------------------ */
+int mmnas_vqa_answer(const float* logits, int B, int A, long ld, const int* slot_idx, long slot_base, int slot_step, int nslots,
+                     const int* qmap, const int* row_ptr, const int* col, const int* k, int nq, long long* pred, int* credit,
+                     int* count, int* err_flag, void* stream);
+int mmnas_vqa_accuracy(const int* credit, const int* qmap, const int* ans_type, const int* ques_type, int N, int nq, int n_at,
+                       int n_qt, long long* totals, int* err_flag, void* stream);
+int mmnas_vqa_answer_targets(const int* ans_ix, int B, int n, int A, float* out, int* err_flag, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement aid (bench.py roofline): while enabled, every kernel launch of the classes below is
  * bracketed by HIP events recorded on the stream it is launched on and tagged with its ALGORITHMIC
  * flops / bytes; mmnas_prof_collect() synchronises the events, sums per class and resets.

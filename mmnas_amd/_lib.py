@@ -219,6 +219,9 @@ SYMBOLS = {
     'mmnas_row_topk': (_i, [_fp, _i, _i, C.c_long, _i, _fp, _fp, _fp]),
     'mmnas_vgd_targets': (_i, [_fp, _fp, _fp, _i, _i, C.c_double, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     'mmnas_vgd_ground': (_i, [_fp] * 5 + [_i, _i, C.c_double] + [_fp] * 7),
+    'mmnas_vqa_answer': (_i, [_fp, _i, _i, C.c_long, _fp, C.c_long, _i, _i] + [_fp] * 4 + [_i] + [_fp] * 5),
+    'mmnas_vqa_accuracy': (_i, [_fp] * 4 + [_i] * 4 + [_fp, _fp, _fp]),
+    'mmnas_vqa_answer_targets': (_i, [_fp, _i, _i, _i, _fp, _fp, _fp]),
     'mmnas_att_op_plan': (_i, [C.POINTER(AttOp), C.POINTER(Plan)]),
     'mmnas_att_op_fwd': (_i, [C.POINTER(AttOp), _fp]),
     'mmnas_att_op_bwd': (_i, [C.POINTER(AttOp), _fp]),
