@@ -791,6 +791,31 @@ int mmnas_vqa_accuracy(const int* credit, const int* qmap, const int* ans_type, 
 int mmnas_vqa_answer_targets(const int* ans_ix, int B, int n, int A, float* out, int* err_flag, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Grounding and retrieval training losses (configs[3] / [4], train_vgd / train_itm; mmnas_amd/losses.py).  One launch forward
+ * (one workgroup; float64 partial sums reduced by shuffles and through LDS, no atomics: bit-identical from call to call), which
+ * also writes the gradients for an upstream gradient of 1, and one launch backward that scales them.  No host synchronisation.
+ *   mmnas_vgd_loss_fwd: train_vgd.py:320-334 with REDUCTION 'sum'.  pred_scores, scores [B,S]; pred_reg, bbox [B,S,4];
+ *     scores_mask [B,S] (smask_full) or [B]; bbox_mask [B,S,4] (bmask_full) or [B,S].  mode 0 = kld: ls = sum xlogy(t m, t m) -
+ *     t m (p m) (F.kl_div: a zero target adds 0), mode 1 = bce: ls = BCE-with-logits over every element (the mask does not enter).
+ *     lr = sum SmoothL1(pred_reg * mask - bbox * mask), beta = 1.  loss_avg: ls /= sum of scores_mask AS GIVEN (B values when not
+ *     full) in kld mode or batch_size in bce mode, lr /= sum of bbox_mask as given; a zero sum gives the reference's 0 / 0 = NaN.
+ *     loss[0] = ls + lam * lr; parts[4] = (ls, lr, sum scores_mask, sum bbox_mask).  dpred_scores [B,S] and dpred_reg [B,S,4]
+ *     (nullable together) = d loss / d predictions.  pred_reg, bbox, a full bbox_mask and dpred_reg are 16-byte aligned.
+ *   mmnas_itm_triplet_loss_fwd: mmnas/utils/itm_loss.py over n scores per role.  mode 0 = BCE_Loss (:4-24): labels 1 / 0 / 0 on
+ *     probabilities, the positive term twice, log clamped at -100 as torch.nn.BCELoss; mean: divided by n.  mode 1 = Margin_Loss
+ *     (:27-37): sum max(0, margin + s_negc - s_pos) + max(0, margin + s_negi - s_pos).  grads (nullable) [3, n] = d loss / d (pos,
+ *     negc, negi); BCE as torch's backward, (s - label) / max((1 - s) s, 1e-12).
+ *   mmnas_loss_grad_scale: out[i] = go[0] * saved[i] (go: device scalar, the loss's upstream gradient) -- the backward of both.
+ * ------------------------------------------------------------------------------------------ */
+int mmnas_vgd_loss_fwd(const float* pred_scores, const float* pred_reg, const float* scores, const float* bbox,
+                       const float* scores_mask, const float* bbox_mask, int B, int S, int smask_full, int bmask_full, int mode,
+                       int loss_avg, double batch_size, double lam, float* loss, float* parts, float* dpred_scores,
+                       float* dpred_reg, void* stream);
+int mmnas_itm_triplet_loss_fwd(const float* scores_pos, const float* scores_negc, const float* scores_negi, long n, int mode,
+                               float margin, int mean, float* loss, float* grads, void* stream);
+int mmnas_loss_grad_scale(const float* saved, const float* go, float* out, size_t n, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement aid (bench.py roofline): while enabled, every kernel launch of the classes below is
  * bracketed by HIP events recorded on the stream it is launched on and tagged with its ALGORITHMIC
  * flops / bytes; mmnas_prof_collect() synchronises the events, sums per class and resets.

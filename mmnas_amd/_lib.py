@@ -222,6 +222,9 @@ SYMBOLS = {
     'mmnas_vqa_answer': (_i, [_fp, _i, _i, C.c_long, _fp, C.c_long, _i, _i] + [_fp] * 4 + [_i] + [_fp] * 5),
     'mmnas_vqa_accuracy': (_i, [_fp] * 4 + [_i] * 4 + [_fp, _fp, _fp]),
     'mmnas_vqa_answer_targets': (_i, [_fp, _i, _i, _i, _fp, _fp, _fp]),
+    'mmnas_vgd_loss_fwd': (_i, [_fp] * 6 + [_i] * 6 + [C.c_double, C.c_double] + [_fp] * 5),
+    'mmnas_itm_triplet_loss_fwd': (_i, [_fp, _fp, _fp, C.c_long, _i, _f, _i, _fp, _fp, _fp]),
+    'mmnas_loss_grad_scale': (_i, [_fp, _fp, _fp, _sz, _fp]),
     'mmnas_att_op_plan': (_i, [C.POINTER(AttOp), C.POINTER(Plan)]),
     'mmnas_att_op_fwd': (_i, [C.POINTER(AttOp), _fp]),
     'mmnas_att_op_bwd': (_i, [C.POINTER(AttOp), _fp]),
