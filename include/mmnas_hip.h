@@ -317,6 +317,11 @@ int mmnas_mixed_sum_bwd(const float* const* outs_host, int n, const float* gate,
                         float* d_active, int active, float* dgate, float* ws, size_t count, void* stream);
 int mmnas_alpha_full_step(float* prob, const float* gate_grad, float* m, float* v, float* prob_grad, int rows,
                           int width, float lr, float beta1, float beta2, float eps, int step, void* stream);
+/* The same with torch Adam's weight_decay -- alpha_optim's ALPHA_WEIGHT_DECAY, search_vqa.py:156-157,194-195: wd * alpha is
+ * added to the gradient the moments see; prob_grad keeps the undecayed dalpha, as alpha_prob.grad does under torch. */
+int mmnas_alpha_full_step_wd(float* prob, const float* gate_grad, float* m, float* v, float* prob_grad, int rows,
+                             int width, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                             void* stream);
 
 /* nn.Embedding backward (hygr_vqa.py:85,105; aten embedding_dense_backward): dW[idx[t], :] += dy[t, :] for the n_tok
  * int64 token indices -- straight into the (already zeroed or accumulating) gradient buffer instead of a dense
@@ -718,6 +723,17 @@ int mmnas_pack_segments_host(const mmnas_segment* segs_host, int nseg, float* st
 int mmnas_adam_step(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1,
                     float beta2, float eps, float weight_decay, const float* sumsq, float max_norm,
                     int step, void* stream);
+/* Fused SGD over a flat fp32 parameter buffer: the NET_OPTIM = 'sgd' branch of the search scripts,
+ * torch.optim.SGD(net_parameters(), NET_LR_BASE, momentum=NET_MOMENTUM, weight_decay=NET_WEIGHT_DECAY).step()
+ * (search_vqa.py:122-127,175-177,300; search_vgd.py / search_itm.py carry the same lines), in torch's order:
+ *   g' = clip * g + weight_decay * p;  buf = momentum * buf + (1 - dampening) * g';
+ *   p -= lr * (nesterov ? g' + momentum * buf : buf).
+ * first != 0: the momentum buffer does not exist yet -- buf = g' (torch's first-step rule; buf is written, not read).
+ * With dampening == 0 a zero-filled buf and first == 0 give the same result.  momentum == 0: buf is neither read nor
+ * written and may be NULL.  sumsq / max_norm: the clip scale of mmnas_adam_step (clip_grad_norm_, search_vqa.py:296-298),
+ * read from the device scalar inside the kernel.  n == 0 returns MMNAS_OK. */
+int mmnas_sgd_step(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float dampening,
+                   float weight_decay, int nesterov, int first, const float* sumsq, float max_norm, void* stream);
 /* out[0] += sum of squares of g[0..n) (for clip_grad_norm_). */
 int mmnas_sumsq(const float* g, size_t n, float* out, void* stream);
 

@@ -193,6 +193,7 @@ SYMBOLS = {
     'mmnas_mixed_sum_fwd': (_i, [C.POINTER(_fp), _i, _fp, _fp, _sz, _fp]),
     'mmnas_mixed_sum_bwd': (_i, [C.POINTER(_fp), _i, _fp, _fp, _fp, _i, _fp, _fp, _sz, _fp]),
     'mmnas_alpha_full_step': (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _f, _f, _f, _f, _i, _fp]),
+    'mmnas_alpha_full_step_wd': (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _f, _f, _f, _f, _f, _i, _fp]),
     'mmnas_embedding_bwd': (_i, [_fp, _fp, _fp, C.c_long, _i, C.c_long, _fp]),
     'mmnas_node_mix_fwd': (_i, [_fp, _fp, _fp, _i, _fp, _fp, _i, _i, _f, _fp]),
     'mmnas_node_mix_bwd': (_i, [_fp, _fp, _fp, _i, _fp, _fp, _fp, _i, _fp, _fp, _i, _i, _f, _fp]),
@@ -250,6 +251,7 @@ SYMBOLS = {
     'mmnas_pack_segments': (_i, [_fp, _i, _fp, _f, _i, _fp]),
     'mmnas_pack_segments_host': (_i, [C.POINTER(Segment), _i, _fp, _f, _i, _fp]),
     'mmnas_adam_step': (_i, [_fp, _fp, _fp, _fp, _sz, _f, _f, _f, _f, _f, _fp, _f, _i, _fp]),
+    'mmnas_sgd_step': (_i, [_fp, _fp, _fp, _sz, _f, _f, _f, _f, _i, _i, _fp, _f, _fp]),
     'mmnas_sumsq': (_i, [_fp, _sz, _fp, _fp]),
     'mmnas_prof_enable': (_i, [_i]),
     'mmnas_prof_collect': (_i, [C.POINTER(ProfStat)]),

@@ -364,7 +364,7 @@ __global__ void __launch_bounds__(256) node_mix_bwd_kernel(NodeMixArgs p, const 
 // one thread per node (row): 'full'-mode architecture gradient + Adam
 __global__ void alpha_full_step_kernel(float* __restrict__ prob, const float* __restrict__ gate_grad, float* __restrict__ m,
                                        float* __restrict__ v, float* __restrict__ prob_grad, int rows, int width, float lr,
-                                       float b1, float b2, float eps, float c1, float c2s) {
+                                       float b1, float b2, float eps, float c1, float c2s, float wd) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= rows) return;
   float* a = prob + (size_t)r * width;
@@ -377,9 +377,10 @@ __global__ void alpha_full_step_kernel(float* __restrict__ prob, const float* __
   for (int i = 0; i < width; ++i) dot += g[i] * (expf(a[i] - mx) / den);
   for (int i = 0; i < width; ++i) {
     const float p = expf(a[i] - mx) / den;
-    const float grad = p * (g[i] - dot);                    // sum_j g_j p_j (delta_ij - p_i), mixed.py:194-198
+    float grad = p * (g[i] - dot);                          // sum_j g_j p_j (delta_ij - p_i), mixed.py:194-198
     if (prob_grad) prob_grad[(size_t)r * width + i] = grad;
     if (p == 0.f && !(a[i] > -INFINITY)) continue;          // padding column: stays -inf
+    if (wd != 0.f) grad += wd * a[i];                       // torch Adam's weight_decay (ALPHA_WEIGHT_DECAY): p.grad itself stays as it is
     const size_t o = (size_t)r * width + i;
     const float mi = b1 * m[o] + (1.f - b1) * grad;
     const float vi = b2 * v[o] + (1.f - b2) * grad * grad;
@@ -433,15 +434,21 @@ extern "C" int mmnas_mixed_sum_bwd(const float* const* outs_host, int n, const f
   return check_launch("mixed_sum_bwd");
 }
 
-extern "C" int mmnas_alpha_full_step(float* prob, const float* gate_grad, float* m, float* v, float* prob_grad, int rows,
-                                     int width, float lr, float beta1, float beta2, float eps, int step, void* stream) {
-  MMNAS_REQUIRE(prob && gate_grad && m && v && step >= 1 && rows >= 0 && width >= 1, MMNAS_E_ARG, "mmnas_alpha_full_step: bad arguments");
+extern "C" int mmnas_alpha_full_step_wd(float* prob, const float* gate_grad, float* m, float* v, float* prob_grad, int rows,
+                                        int width, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                                        void* stream) {
+  MMNAS_REQUIRE(prob && gate_grad && m && v && step >= 1 && rows >= 0 && width >= 1, MMNAS_E_ARG, "mmnas_alpha_full_step / mmnas_alpha_full_step_wd: bad arguments");
   if (rows == 0) return MMNAS_OK;
   const float c1 = 1.f - powf(beta1, (float)step);
   const float c2s = sqrtf(1.f - powf(beta2, (float)step));
   MMNAS_LAUNCH(alpha_full_step_kernel, dim3(cdiv(rows, 64)), dim3(64), 0, (hipStream_t)stream, prob, gate_grad, m, v, prob_grad,
-               rows, width, lr, beta1, beta2, eps, c1, c2s);
+               rows, width, lr, beta1, beta2, eps, c1, c2s, weight_decay);
   return check_launch("alpha_full_step");
+}
+
+extern "C" int mmnas_alpha_full_step(float* prob, const float* gate_grad, float* m, float* v, float* prob_grad, int rows,
+                                     int width, float lr, float beta1, float beta2, float eps, int step, void* stream) {
+  return mmnas_alpha_full_step_wd(prob, gate_grad, m, v, prob_grad, rows, width, lr, beta1, beta2, eps, 0.f, step, stream);
 }
 
 

@@ -1,6 +1,6 @@
 // Error plumbing, ABI version, and the small utility kernels of the C ABI:
 // dropout-mask materialisation (tests / mask replay), segment pack/unpack for the data-parallel
-// gradient exchange, fused Adam and sum-of-squares for the optimizer step.
+// gradient exchange, fused Adam / SGD and sum-of-squares for the optimizer step.
 #include <stdarg.h>
 #include <string.h>
 #include <mutex>
@@ -195,6 +195,55 @@ __global__ void __launch_bounds__(256) adam4_kernel(float4* __restrict__ p, cons
     m[i] = mi; v[i] = vi; p[i] = pi;
   }
 }
+// torch.optim.SGD (momentum, dampening, nesterov, weight decay) with the clip scale read from the device scalar, in
+// torch's order of operations.  `first`: the momentum buffer does not exist yet -- torch's first step sets buf = g'
+// (no dampening).  MOM == false neither reads nor writes buf.
+template <bool MOM>
+__device__ __forceinline__ void sgd_one(float& pi, float gi, float& bi, float gscale, float lr, float mom, float damp, float wd,
+                                        bool nesterov, bool first) {
+  // (explicit fmaf: each torch statement -- add(p, alpha=wd), mul_(momentum).add_(g', alpha=1 - dampening), add_(buf, alpha=-lr) --
+  //  is one rounding of a + alpha * b in ATen; written out so that contraction cannot pick another grouping)
+  gi *= gscale;
+  if (wd != 0.f) gi = fmaf(wd, pi, gi);
+  if (MOM) {
+    bi = first ? gi : fmaf(1.f - damp, gi, mom * bi);
+    gi = nesterov ? fmaf(mom, bi, gi) : bi;
+  }
+  pi = fmaf(-lr, gi, pi);
+}
+template <bool MOM>
+__global__ void sgd_kernel(float* p, const float* g, float* buf, size_t n, float lr, float mom, float damp, float wd, int nesterov,
+                           int first, const float* sumsq, float max_norm) {
+  float gscale = 1.f;
+  if (sumsq) gscale = fminf(1.f, max_norm / (sqrtf(*sumsq) + 1e-6f));
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    float pi = p[i], bi = 0.f;
+    if (MOM && !first) bi = buf[i];
+    sgd_one<MOM>(pi, g[i], bi, gscale, lr, mom, damp, wd, nesterov != 0, first != 0);
+    if (MOM) buf[i] = bi;
+    p[i] = pi;
+  }
+}
+// four consecutive elements per thread and pass, as adam4_kernel: 20 bytes of traffic per element (12 without momentum)
+template <bool MOM>
+__global__ void __launch_bounds__(256) sgd4_kernel(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ buf,
+                                                   size_t n4, float lr, float mom, float damp, float wd, int nesterov, int first,
+                                                   const float* sumsq, float max_norm) {
+  float gscale = 1.f;
+  if (sumsq) gscale = fminf(1.f, max_norm / (sqrtf(*sumsq) + 1e-6f));
+  const bool nest = nesterov != 0, fst = first != 0;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+    float4 pi = p[i], bi = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 gi = g[i];
+    if (MOM && !fst) bi = buf[i];
+    sgd_one<MOM>(pi.x, gi.x, bi.x, gscale, lr, mom, damp, wd, nest, fst);
+    sgd_one<MOM>(pi.y, gi.y, bi.y, gscale, lr, mom, damp, wd, nest, fst);
+    sgd_one<MOM>(pi.z, gi.z, bi.z, gscale, lr, mom, damp, wd, nest, fst);
+    sgd_one<MOM>(pi.w, gi.w, bi.w, gscale, lr, mom, damp, wd, nest, fst);
+    if (MOM) buf[i] = bi;
+    p[i] = pi;
+  }
+}
 __global__ void __launch_bounds__(256) sumsq4_kernel(const float4* __restrict__ g, size_t n4, float* out) {
   float s0 = 0.f, s1 = 0.f;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
@@ -351,6 +400,38 @@ extern "C" int mmnas_adam_step(float* p, const float* g, float* m, float* v, siz
                  beta2, eps, weight_decay, sumsq, max_norm, c1, c2);
   }
   return check_launch("adam_step");
+}
+
+extern "C" int mmnas_sgd_step(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float dampening,
+                              float weight_decay, int nesterov, int first, const float* sumsq, float max_norm, void* stream) {
+  if (n == 0) return MMNAS_OK;
+  const bool mom = momentum != 0.f;
+  MMNAS_REQUIRE(p && g && (buf || !mom), MMNAS_E_ARG, "mmnas_sgd_step: null pointer (buf may be null only with momentum == 0)");
+  MMNAS_REQUIRE(!nesterov || (mom && dampening == 0.f), MMNAS_E_ARG, "mmnas_sgd_step: nesterov needs momentum != 0 and dampening == 0");
+  // 16-byte path for the aligned body, the scalar kernel for a misaligned call or the tail (< 4 elements)
+  const bool al16 = ((((uintptr_t)p | (uintptr_t)g | (mom ? (uintptr_t)buf : 0)) & 15) == 0);
+  const size_t n4 = al16 ? n / 4 : 0, done = 4 * n4;
+  hipStream_t st = (hipStream_t)stream;
+  if (n4) {
+    const int blocks4 = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
+    if (mom)
+      MMNAS_LAUNCH(sgd4_kernel<true>, dim3(blocks4), dim3(256), 0, st, (float4*)p, (const float4*)g, (float4*)buf, n4, lr, momentum,
+                   dampening, weight_decay, nesterov, first, sumsq, max_norm);
+    else
+      MMNAS_LAUNCH(sgd4_kernel<false>, dim3(blocks4), dim3(256), 0, st, (float4*)p, (const float4*)g, (float4*)nullptr, n4, lr, momentum,
+                   dampening, weight_decay, nesterov, first, sumsq, max_norm);
+  }
+  if (done < n) {
+    const size_t r = n - done;
+    const int blocks = (int)((r + 255) / 256 < 4096 ? (r + 255) / 256 : 4096);
+    if (mom)
+      MMNAS_LAUNCH(sgd_kernel<true>, dim3(blocks), dim3(256), 0, st, p + done, g + done, buf + done, r, lr, momentum, dampening,
+                   weight_decay, nesterov, first, sumsq, max_norm);
+    else
+      MMNAS_LAUNCH(sgd_kernel<false>, dim3(blocks), dim3(256), 0, st, p + done, g + done, (float*)nullptr, r, lr, momentum, dampening,
+                   weight_decay, nesterov, first, sumsq, max_norm);
+  }
+  return check_launch("sgd_step");
 }
 
 extern "C" int mmnas_sumsq(const float* g, size_t n, float* out, void* stream) {

@@ -13,6 +13,8 @@ implementation:
       - gradients live in one flat buffer (dp.SupernetReducer); clip_grad_norm_ + Adam are two kernels (optim.FlatAdam);
       - the arch step's alpha gradient + alpha_optim.step() are one kernel (ArchAdam, mode 'full').
     Pinned against the reference loop itself by tests/golden/traj.npz (tests/test_harness_gpu.py::test_bilevel_trajectory_vs_reference_loop).
+    net_optim='sgd' is the scripts' other NET_OPTIM branch (search_vqa.py:122-131,175-177,228-244,261): optim.FlatSGD +
+    optim.CosineSchedule stepped by begin_epoch(); pinned by tests/golden/traj_sgd.npz (tests/test_sgd_gpu.py).
   * itm_triplet_step -- train_itm.py:380-391: three forwards (positive, negative caption, negative image), BCE_Loss.
   * BCE_Loss -- mmnas/utils/itm_loss.py:4-24.  vgd_loss -- train_vgd.py:316-333.
 """
@@ -22,7 +24,7 @@ import torch.nn.functional as F
 
 from . import dp, ops
 from .model.mixed import MixedOp
-from .optim import FlatAdam, WarmupOptimizer
+from .optim import CosineSchedule, FlatAdam, FlatSGD, WarmupOptimizer
 
 
 class BCEWithLogitsSum(nn.Module):
@@ -105,8 +107,9 @@ class ArchAdam:
     """alpha_optim of search_vqa.py:194 (torch.optim.Adam over alpha_prob_parameters, lr 0.1, betas (0, 0.999)) fused
     with Net_Search.set_arch_param_grad() for ALPHA_BINARY_MODE 'full': one kernel over the [n_nodes, width] blocks."""
 
-    def __init__(self, net, lr=0.1, betas=(0.0, 0.999), eps=1e-8):
+    def __init__(self, net, lr=0.1, betas=(0.0, 0.999), eps=1e-8, weight_decay=0):
         self.net, self.lr, self.betas, self.eps = net, lr, betas, eps
+        self.weight_decay = weight_decay      # ALPHA_WEIGHT_DECAY (search_vqa.py:156-157,195)
         prob, _ = net._flat_alphas()
         self.m = torch.zeros_like(prob)
         self.v = torch.zeros_like(prob)
@@ -121,7 +124,7 @@ class ArchAdam:
             if g is not None and g.data_ptr() != gg[i].data_ptr():
                 gg[i, :m.n_choices].copy_(g)
         self.steps += 1
-        ops.alpha_full_step(prob, gg, self.m, self.v, pg, self.lr, self.betas, self.eps, self.steps)
+        ops.alpha_full_step(prob, gg, self.m, self.v, pg, self.lr, self.betas, self.eps, self.steps, self.weight_decay)
         for i, m in enumerate(net.redundant_modules):
             m.alpha_prob.grad = pg[i, :m.n_choices]
             m.alpha_version += 1                          # (the update wrote through the flat block: drop the sampling cache)
@@ -136,7 +139,7 @@ class ArchAdam:
                 n = m.n_choices
                 state[i] = {'step': torch.tensor(float(self.steps)), 'exp_avg': self.m[i, :n].clone(),
                             'exp_avg_sq': self.v[i, :n].clone()}
-        group = {'lr': self.lr, 'betas': tuple(self.betas), 'eps': self.eps, 'weight_decay': 0, 'amsgrad': False,
+        group = {'lr': self.lr, 'betas': tuple(self.betas), 'eps': self.eps, 'weight_decay': self.weight_decay, 'amsgrad': False,
                  'maximize': False, 'foreach': None, 'capturable': False, 'differentiable': False, 'fused': None,
                  'params': list(range(len(mods)))}
         return {'state': state, 'param_groups': [group]}
@@ -149,6 +152,7 @@ class ArchAdam:
         if len(order) != len(mods):
             raise ValueError('ArchAdam.load_state_dict: %d parameters in the file, %d alpha blocks here' % (len(order), len(mods)))
         self.lr, self.betas, self.eps = g0.get('lr', self.lr), tuple(g0.get('betas', self.betas)), g0.get('eps', self.eps)
+        self.weight_decay = g0.get('weight_decay', self.weight_decay)
         self.m.zero_()
         self.v.zero_()
         steps = set()
@@ -201,33 +205,80 @@ class TrainLoop:
 
 
 class SearchLoop:
-    """The bilevel NAS loop body of search_vqa.py:279-337 for one data-parallel rank."""
+    """The bilevel NAS loop body of search_vqa.py:279-337 for one data-parallel rank.
+
+    net_optim: the scripts' NET_OPTIM.  'wadam' (default): warm-up Adam, `net_lr` = NET_LR_BASE, decay() by the caller.
+    'sgd': torch.optim.SGD(net_lr, momentum=net_momentum, weight_decay=net_weight_decay) as FlatSGD under
+    CosineAnnealingLR(max_epoch, eta_min=net_lr_min) as CosineSchedule; call begin_epoch(epoch) at the start of every epoch
+    (search_vqa.py:261-262).  To resume, pass start_epoch=CKPT_EPOCH and load the checkpoint's 'net_optim' into
+    `loop.net_optim` (search_vqa.py:226-231).  net_weight_decay / alpha_weight_decay: NET_WEIGHT_DECAY / ALPHA_WEIGHT_DECAY."""
 
     def __init__(self, net, loss_fn=None, net_lr=4e-4, net_betas=(0.9, 0.98), net_eps=1e-9, clip=1.0, epoch_steps=1000,
                  warmup=True, alpha_lr=0.1, alpha_betas=(0.0, 0.999), alpha_every=5, arch_mode='full', group=None,
-                 absent_grads='zero', n_buckets=3, force_collectives=False):
+                 absent_grads='zero', n_buckets=3, force_collectives=False, net_optim='wadam', net_momentum=0.9,
+                 net_weight_decay=0.0, net_lr_min=0.0005, max_epoch=None, start_epoch=0, alpha_weight_decay=0.0):
         if arch_mode not in ('full', 'two'):
             raise ValueError("ALPHA_BINARY_MODE is 'full' or 'two' (search_vqa.py:151), got %r" % (arch_mode,))
+        if net_optim not in ('wadam', 'sgd'):
+            raise ValueError("NET_OPTIM is 'wadam' or 'sgd' (search_vqa.py:117-118), got %r" % (net_optim,))
+        if net_optim == 'sgd' and max_epoch is None:
+            raise ValueError("net_optim='sgd' anneals the rate over MAX_EPOCH epochs (search_vqa.py:131,243-244): pass max_epoch")
         self.net = net
         self.loss_fn = fused_loss(loss_fn if loss_fn is not None else nn.BCEWithLogitsLoss(reduction='sum'))
         dense = absent_grads == 'zero'
         self.reducer = dp.SupernetReducer(net, group=group, n_buckets=n_buckets, force_collectives=force_collectives,
                                           attach_all=dense)
         net.keep_candidate_grads = dense
-        self.net_optim = WarmupOptimizer(net_lr, FlatAdam(self.reducer.fg.params, betas=net_betas, eps=net_eps,
-                                                          grads=self.reducer.fg, absent_grads=absent_grads),
-                                         epoch_steps=epoch_steps, warmup=warmup, max_norm=clip if clip and clip > 0 else None)
+        max_norm = self._max_norm = clip if clip and clip > 0 else None
+        self.lr_scheduler = None
+        if net_optim == 'sgd':
+            # the script's net_optim IS the torch SGD here (no WarmupOptimizer around it): state_dict() / load_state_dict()
+            # are the optimizer's own, the clip travels with every step
+            self.net_optim = FlatSGD(self.reducer.fg.params, lr=net_lr, momentum=net_momentum, weight_decay=net_weight_decay,
+                                     grads=self.reducer.fg, absent_grads=absent_grads)
+            if start_epoch:
+                self.net_optim.param_groups[0]['initial_lr'] = net_lr      # (what the checkpoint's param group carries)
+            self.lr_scheduler = CosineSchedule(self.net_optim, max_epoch, eta_min=net_lr_min,
+                                               last_epoch=start_epoch if start_epoch else -1)
+            # (a resumed CosineAnnealingLR counts its constructor's step on top of last_epoch, a fresh one starts at 0)
+            self._epoch_shift = self.lr_scheduler.last_epoch - start_epoch
+        else:
+            self.net_optim = WarmupOptimizer(net_lr, FlatAdam(self.reducer.fg.params, betas=net_betas, eps=net_eps,
+                                                              weight_decay=net_weight_decay, grads=self.reducer.fg,
+                                                              absent_grads=absent_grads),
+                                             epoch_steps=epoch_steps, warmup=warmup, max_norm=max_norm)
         # 'full' (the shipped setting): alpha gradient + Adam as one kernel over the [n_nodes, width] blocks.  'two': the
         # reference's own statements -- MixedOp.set_arch_param_grad over the sampled pair, torch Adam on the alpha
         # parameters, rescale_updated_arch_param (search_vqa.py:330-334, mixed.py:179-208)
         if arch_mode == 'full':
-            self.alpha_optim = ArchAdam(net, alpha_lr, alpha_betas)
+            self.alpha_optim = ArchAdam(net, alpha_lr, alpha_betas, weight_decay=alpha_weight_decay)
         else:
             net._flat_alphas()          # (the parameters' storage moves into the flat blocks before Adam sees them)
-            self.alpha_optim = torch.optim.Adam(list(net.alpha_prob_parameters()), alpha_lr, betas=tuple(alpha_betas))
+            self.alpha_optim = torch.optim.Adam(list(net.alpha_prob_parameters()), alpha_lr, betas=tuple(alpha_betas),
+                                                weight_decay=alpha_weight_decay)
         self.alpha_every = alpha_every
         self.arch_mode = arch_mode
         self.steps = 0
+
+    def begin_epoch(self, epoch=None):
+        """The top of the scripts' epoch loop (search_vqa.py:261-265): 'sgd' steps the cosine schedule -- before the epoch's
+        weight steps; 'wadam' has nothing to do here (its decay() at the epochs of NET_LR_DECAY_LIST stays the caller's).
+        `epoch` (0-based, the scripts' loop variable) is checked against the schedule's own count when given: the schedule
+        moves by one per call, so an epoch skipped or begun twice is an error, not a silently shifted rate."""
+        if self.lr_scheduler is None:
+            return
+        if epoch is not None and epoch + self._epoch_shift != self.lr_scheduler.last_epoch:
+            raise ValueError('begin_epoch(%d): the cosine schedule stands before epoch %d (start_epoch plus the epochs begun so '
+                             'far)' % (epoch, self.lr_scheduler.last_epoch - self._epoch_shift))
+        self.lr_scheduler.step()
+
+    def _net_step(self):
+        # whatever `self.net_optim` is NOW (a caller may replace it): a bare FlatSGD takes the clip with every step, the
+        # WarmupOptimizer carries its own
+        if isinstance(self.net_optim, FlatSGD):
+            self.net_optim.step(max_norm=self._max_norm)
+        else:
+            self.net_optim.step()
 
     def _sample(self, plan):
         if plan is None:
@@ -247,7 +298,7 @@ class SearchLoop:
         loss.backward()
         red.finish_weight_step()
         if optimize:
-            self.net_optim.step()
+            self._net_step()
         self.steps += 1
         return loss
 

@@ -1616,8 +1616,14 @@ def mixed_sum(gate, outs, active):
     return MixedSumFn.apply(gate, outs[active], active, len(outs), idx, *[outs[i] for i in idx])
 
 
-def alpha_full_step(prob, gate_grad, m, v, prob_grad, lr, betas, eps, step):
-    """All nodes' architecture update in one launch (mmnas_alpha_full_step): prob/gate_grad/m/v [nodes, width]."""
+def alpha_full_step(prob, gate_grad, m, v, prob_grad, lr, betas, eps, step, weight_decay=0.0):
+    """All nodes' architecture update in one launch (mmnas_alpha_full_step): prob/gate_grad/m/v [nodes, width].
+    weight_decay != 0: torch Adam's decay folded into the same launch (mmnas_alpha_full_step_wd)."""
+    if weight_decay:
+        L.check(L.lib().mmnas_alpha_full_step_wd(L.fptr(prob), L.fptr(gate_grad), L.fptr(m), L.fptr(v), L.fptr(prob_grad),
+                                                 prob.shape[0], prob.shape[1], float(lr), float(betas[0]), float(betas[1]),
+                                                 float(eps), float(weight_decay), int(step), L.stream()))
+        return
     L.check(L.lib().mmnas_alpha_full_step(L.fptr(prob), L.fptr(gate_grad), L.fptr(m), L.fptr(v), L.fptr(prob_grad),
                                           prob.shape[0], prob.shape[1], float(lr), float(betas[0]), float(betas[1]),
                                           float(eps), int(step), L.stream()))
