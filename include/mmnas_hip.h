@@ -322,6 +322,21 @@ int mmnas_alpha_full_step(float* prob, const float* gate_grad, float* m, float* 
 int mmnas_alpha_full_step_wd(float* prob, const float* gate_grad, float* m, float* v, float* prob_grad, int rows,
                              int width, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                              void* stream);
+/* ALPHA_BINARY_MODE 'two' (mixed.py:179-208, search_vqa.py:330-335): set_arch_param_grad over the sampled pair, the
+ * alpha_optim.step() of torch Adam and rescale_updated_arch_param of every node in one launch.  pair_host is a HOST array of
+ * rows * 2 ints, (active, inactive) column per row, read at call time and carried in the kernel arguments (rows <= 128, else
+ * MMNAS_E_SHAPE).  For row r with pair (i, j): p = softmax(a_i, a_j) over the pair alone, gp = g * p on the pair,
+ * dalpha_i = gp_i - p_i (gp_i + gp_j), likewise j, 0 in every other column; prob_grad (nullable) receives the whole row (written,
+ * not accumulated).  Adam then steps EVERY non-padding column of the row (what torch Adam does with a gradient that is zero
+ * outside the pair: moments decay, weight_decay * alpha enters the moments but not prob_grad); padding columns (-inf) keep their
+ * logit and moments.  Last, offset = logsumexp(new a_i, a_j) - logsumexp(old a_i, a_j) is taken from both logits of the pair,
+ * which keeps the pair's probability mass.  i == j, a column outside 0..width-1 or step < 1: MMNAS_E_ARG, nothing is launched
+ * (a pair that names a padding column is the caller's to reject: only it knows each node's width).  rows == 0: MMNAS_OK.
+ * beta1 / beta2 are read as the decimals the caller wrote (the shortest decimal that rounds to the float: 0.999f -> 0.999), so
+ * that 1 - beta2 and the bias corrections -- and with them exp_avg_sq -- are torch Adam's, which forms them from Python floats. */
+int mmnas_alpha_two_step(float* prob, const float* gate_grad, float* m, float* v, float* prob_grad, int rows, int width,
+                         const int* pair_host, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                         void* stream);
 
 /* nn.Embedding backward (hygr_vqa.py:85,105; aten embedding_dense_backward): dW[idx[t], :] += dy[t, :] for the n_tok
  * int64 token indices -- straight into the (already zeroed or accumulating) gradient buffer instead of a dense

@@ -3,8 +3,12 @@
 //     the inner product <dL/dout, o_j>, which the reference obtains from ~10 ATen kernels per candidate
 //     (select, mul, add, and their autograd: expand, mul, sum);
 //   * the architecture-parameter update of all nodes in one launch: dL/dalpha from dL/dgate (mixed.py:171-198,
-//     'full' mode) followed by the Adam step of alpha_optim (search_vqa.py:194,331-332).
+//     'full' mode) followed by the Adam step of alpha_optim (search_vqa.py:194,331-332); for 'two' mode the gradient
+//     over the sampled pair, the same Adam step and the pair's rescale (mixed.py:179-208, search_vqa.py:330-335).
 // HBM-bound streaming kernels (one pass over the candidate outputs).
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include "common.h"
 
@@ -389,6 +393,51 @@ __global__ void alpha_full_step_kernel(float* __restrict__ prob, const float* __
   }
 }
 
+// one thread per node (row): 'two'-mode architecture gradient over the sampled pair + Adam over the row + the pair's
+// mass-preserving rescale (mixed.py:179-208, search_vqa.py:330-335).  The pairs travel in the kernel arguments.
+constexpr int ALPHA_TWO_MAX_ROWS = 128;                    // mmnas_onehot_rows' limit: 1 KB of kernel arguments
+struct AlphaPairArgs { int ij[ALPHA_TWO_MAX_ROWS * 2]; };   // (active, inactive) per row
+
+__global__ void alpha_two_step_kernel(float* __restrict__ prob, const float* __restrict__ gate_grad, float* __restrict__ m,
+                                      float* __restrict__ v, float* __restrict__ prob_grad, int rows, int width, float lr,
+                                      float b1, float b2, float omb1, float omb2, float eps, float c1, float c2s, float wd,
+                                      AlphaPairArgs pa) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= rows) return;
+  const int pi = pa.ij[2 * r], pj = pa.ij[2 * r + 1];       // (checked on the host: 0 <= pi != pj < width)
+  float* a = prob + (size_t)r * width;
+  const float* g = gate_grad + (size_t)r * width;
+  const float oi = a[pi], oj = a[pj];                       // the pair's logits before Adam
+  const float mx = fmaxf(oi, oj);
+  const float ei = expf(oi - mx), ej = expf(oj - mx);
+  const float den = ei + ej;
+  const float si = ei / den, sj = ej / den;                 // softmax over the pair only (mixed.py:181)
+  const float gpi = g[pi] * si, gpj = g[pj] * sj;
+  const float dot = gpi + gpj;
+  const float gi = gpi - si * dot, gj = gpj - sj * dot;     // sum_k g_k p_k (delta_ik - p_i) over the pair (mixed.py:182-186)
+  for (int i = 0; i < width; ++i) {
+    float grad = i == pi ? gi : (i == pj ? gj : 0.f);
+    const size_t o = (size_t)r * width + i;
+    if (prob_grad) prob_grad[o] = grad;
+    const float ai = a[i];
+    if (!(ai > -INFINITY)) continue;                        // padding column: stays -inf, its moments untouched
+    if (wd != 0.f) grad += wd * ai;                         // torch Adam's weight_decay: p.grad itself stays as it is
+    const float mi = b1 * m[o] + omb1 * grad;               // omb = 1 - beta, formed on the host (see mmnas_alpha_two_step)
+    const float vi = b2 * v[o] + omb2 * grad * grad;
+    m[o] = mi; v[o] = vi;
+    a[i] = ai - (lr / c1) * mi / (sqrtf(vi) / c2s + eps);
+  }
+  // rescale_updated_arch_param (mixed.py:200-208): offset = logsumexp(new pair) - logsumexp(old pair), in double as the
+  // reference's math.log / math.exp; the differences of the maxima and of the logs are taken apart, so nothing cancels
+  const float ni = a[pi], nj = a[pj];
+  const float nmx = fmaxf(ni, nj);
+  const double nden = exp((double)ni - (double)nmx) + exp((double)nj - (double)nmx);
+  const double oden = exp((double)oi - (double)mx) + exp((double)oj - (double)mx);
+  const double off = ((double)nmx - (double)mx) + log(nden / oden);
+  a[pi] = (float)((double)ni - off);
+  a[pj] = (float)((double)nj - off);
+}
+
 }  // namespace mmnas
 
 using namespace mmnas;
@@ -449,6 +498,42 @@ extern "C" int mmnas_alpha_full_step_wd(float* prob, const float* gate_grad, flo
 extern "C" int mmnas_alpha_full_step(float* prob, const float* gate_grad, float* m, float* v, float* prob_grad, int rows,
                                      int width, float lr, float beta1, float beta2, float eps, int step, void* stream) {
   return mmnas_alpha_full_step_wd(prob, gate_grad, m, v, prob_grad, rows, width, lr, beta1, beta2, eps, 0.f, step, stream);
+}
+
+// A float coefficient as the caller wrote it: the shortest decimal that rounds back to the float, read as a double
+// (0.999f -> 0.999).  1 - 0.999f is 1.3e-5 (relative) away from 0.001, and with it exp_avg_sq from what torch Adam -- which
+// forms 1 - beta2 and the bias corrections from Python floats -- keeps in its checkpoint.
+static double decimal_of(float x) {
+  char buf[40];
+  for (int digits = 1; digits <= 9; ++digits) {
+    snprintf(buf, sizeof(buf), "%.*g", digits, (double)x);
+    if (strtof(buf, nullptr) == x) break;
+  }
+  return strtod(buf, nullptr);
+}
+
+extern "C" int mmnas_alpha_two_step(float* prob, const float* gate_grad, float* m, float* v, float* prob_grad, int rows,
+                                    int width, const int* pair_host, float lr, float beta1, float beta2, float eps,
+                                    float weight_decay, int step, void* stream) {
+  MMNAS_REQUIRE(rows >= 0 && rows <= ALPHA_TWO_MAX_ROWS, MMNAS_E_SHAPE, "mmnas_alpha_two_step: rows=%d (0..%d)", rows, ALPHA_TWO_MAX_ROWS);
+  MMNAS_REQUIRE(step >= 1 && width >= 2, MMNAS_E_ARG, "mmnas_alpha_two_step: step=%d (>= 1) width=%d (>= 2)", step, width);
+  if (rows == 0) return MMNAS_OK;
+  MMNAS_REQUIRE(prob && gate_grad && m && v && pair_host, MMNAS_E_ARG, "mmnas_alpha_two_step: null pointer");
+  AlphaPairArgs pa;
+  memset(&pa, 0, sizeof(pa));
+  for (int r = 0; r < rows; ++r) {
+    const int i = pair_host[2 * r], j = pair_host[2 * r + 1];
+    MMNAS_REQUIRE(i >= 0 && i < width && j >= 0 && j < width && i != j, MMNAS_E_ARG,
+                  "mmnas_alpha_two_step: row %d: pair (%d, %d) must be two different columns of 0..%d", r, i, j, width - 1);
+    pa.ij[2 * r] = i;
+    pa.ij[2 * r + 1] = j;
+  }
+  const double b1 = decimal_of(beta1), b2 = decimal_of(beta2);
+  const float c1 = (float)(1.0 - pow(b1, (double)step));
+  const float c2s = (float)sqrt(1.0 - pow(b2, (double)step));
+  MMNAS_LAUNCH(alpha_two_step_kernel, dim3(cdiv(rows, 64)), dim3(64), 0, (hipStream_t)stream, prob, gate_grad, m, v, prob_grad,
+               rows, width, lr, beta1, beta2, (float)(1.0 - b1), (float)(1.0 - b2), eps, c1, c2s, weight_decay, pa);
+  return check_launch("alpha_two_step");
 }
 
 

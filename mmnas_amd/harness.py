@@ -11,7 +11,8 @@ implementation:
         Their arithmetic consequence -- torch Adam steps EVERY net parameter at every step, unsampled candidates
         included (zero gradient, decaying moments, stale-momentum motion) -- is kept by FlatAdam(absent_grads='zero');
       - gradients live in one flat buffer (dp.SupernetReducer); clip_grad_norm_ + Adam are two kernels (optim.FlatAdam);
-      - the arch step's alpha gradient + alpha_optim.step() are one kernel (ArchAdam, mode 'full').
+      - the arch step's alpha gradient + alpha_optim.step() are one kernel (ArchAdam, mode 'full'; mode 'two', with the
+        pair's rescale in the same kernel, under fused_arch_update=True).
     Pinned against the reference loop itself by tests/golden/traj.npz (tests/test_harness_gpu.py::test_bilevel_trajectory_vs_reference_loop).
     net_optim='sgd' is the scripts' other NET_OPTIM branch (search_vqa.py:122-131,175-177,228-244,261): optim.FlatSGD +
     optim.CosineSchedule stepped by begin_epoch(); pinned by tests/golden/traj_sgd.npz (tests/test_sgd_gpu.py).
@@ -105,9 +106,15 @@ def hard_negative_indices(scores, neg_idx, hard_size):
 
 class ArchAdam:
     """alpha_optim of search_vqa.py:194 (torch.optim.Adam over alpha_prob_parameters, lr 0.1, betas (0, 0.999)) fused
-    with Net_Search.set_arch_param_grad() for ALPHA_BINARY_MODE 'full': one kernel over the [n_nodes, width] blocks."""
+    with Net_Search.set_arch_param_grad() for ALPHA_BINARY_MODE 'full': one kernel over the [n_nodes, width] blocks.
+    mode='two': the same for ALPHA_BINARY_MODE 'two' -- set_arch_param_grad over each node's sampled pair, the Adam step and
+    rescale_updated_arch_param (search_vqa.py:330-335, mixed.py:179-208) as one kernel (ops.alpha_two_step); the pairs are
+    read from the nodes' active_index / inactive_index when step() runs.  The checkpoint format is the same in both modes."""
 
-    def __init__(self, net, lr=0.1, betas=(0.0, 0.999), eps=1e-8, weight_decay=0):
+    def __init__(self, net, lr=0.1, betas=(0.0, 0.999), eps=1e-8, weight_decay=0, mode='full'):
+        if mode not in ('full', 'two'):
+            raise ValueError("ArchAdam: mode is 'full' or 'two', got %r" % (mode,))
+        self.mode = mode
         self.net, self.lr, self.betas, self.eps = net, lr, betas, eps
         self.weight_decay = weight_decay      # ALPHA_WEIGHT_DECAY (search_vqa.py:156-157,195)
         prob, _ = net._flat_alphas()
@@ -115,16 +122,34 @@ class ArchAdam:
         self.v = torch.zeros_like(prob)
         self.steps = 0
 
+    def _sampled_pairs(self):
+        pairs = []
+        for i, m in enumerate(self.net.redundant_modules):
+            act, inact = m.active_index, m.inactive_index
+            if not act or not inact or len(act) != 1 or len(inact) != 1:
+                raise ValueError("ArchAdam(mode='two'): node %d has no sampled pair (active_index %r, inactive_index %r): "
+                                 "sample with MixedOp.MODE = 'two' first" % (i, act, inact))
+            a, b = int(act[0]), int(inact[0])
+            if a == b or not (0 <= a < m.n_choices and 0 <= b < m.n_choices):
+                raise ValueError("ArchAdam(mode='two'): node %d: pair (%d, %d) must be two different candidates of 0..%d"
+                                 % (i, a, b, m.n_choices - 1))
+            pairs.append((a, b))
+        return pairs
+
     def step(self):
         net = self.net
         prob, _ = net._flat_alphas()
         gg, pg = net._flat_grads
+        pairs = self._sampled_pairs() if self.mode == 'two' else None      # (before anything is written)
         for i, m in enumerate(net.redundant_modules):    # gate gradients autograd produced outside the block
             g = m.alpha_gate.grad
             if g is not None and g.data_ptr() != gg[i].data_ptr():
                 gg[i, :m.n_choices].copy_(g)
         self.steps += 1
-        ops.alpha_full_step(prob, gg, self.m, self.v, pg, self.lr, self.betas, self.eps, self.steps, self.weight_decay)
+        if pairs is not None:
+            ops.alpha_two_step(prob, gg, self.m, self.v, pg, pairs, self.lr, self.betas, self.eps, self.steps, self.weight_decay)
+        else:
+            ops.alpha_full_step(prob, gg, self.m, self.v, pg, self.lr, self.betas, self.eps, self.steps, self.weight_decay)
         for i, m in enumerate(net.redundant_modules):
             m.alpha_prob.grad = pg[i, :m.n_choices]
             m.alpha_version += 1                          # (the update wrote through the flat block: drop the sampling cache)
@@ -211,12 +236,15 @@ class SearchLoop:
     'sgd': torch.optim.SGD(net_lr, momentum=net_momentum, weight_decay=net_weight_decay) as FlatSGD under
     CosineAnnealingLR(max_epoch, eta_min=net_lr_min) as CosineSchedule; call begin_epoch(epoch) at the start of every epoch
     (search_vqa.py:261-262).  To resume, pass start_epoch=CKPT_EPOCH and load the checkpoint's 'net_optim' into
-    `loop.net_optim` (search_vqa.py:226-231).  net_weight_decay / alpha_weight_decay: NET_WEIGHT_DECAY / ALPHA_WEIGHT_DECAY."""
+    `loop.net_optim` (search_vqa.py:226-231).  net_weight_decay / alpha_weight_decay: NET_WEIGHT_DECAY / ALPHA_WEIGHT_DECAY.
+    fused_arch_update (arch_mode='two' only): the architecture update as ArchAdam(mode='two') instead of the per-node
+    statements around torch Adam; the checkpoints of the two are interchangeable."""
 
     def __init__(self, net, loss_fn=None, net_lr=4e-4, net_betas=(0.9, 0.98), net_eps=1e-9, clip=1.0, epoch_steps=1000,
                  warmup=True, alpha_lr=0.1, alpha_betas=(0.0, 0.999), alpha_every=5, arch_mode='full', group=None,
                  absent_grads='zero', n_buckets=3, force_collectives=False, net_optim='wadam', net_momentum=0.9,
-                 net_weight_decay=0.0, net_lr_min=0.0005, max_epoch=None, start_epoch=0, alpha_weight_decay=0.0):
+                 net_weight_decay=0.0, net_lr_min=0.0005, max_epoch=None, start_epoch=0, alpha_weight_decay=0.0,
+                 fused_arch_update=False):
         if arch_mode not in ('full', 'two'):
             raise ValueError("ALPHA_BINARY_MODE is 'full' or 'two' (search_vqa.py:151), got %r" % (arch_mode,))
         if net_optim not in ('wadam', 'sgd'):
@@ -250,8 +278,13 @@ class SearchLoop:
         # 'full' (the shipped setting): alpha gradient + Adam as one kernel over the [n_nodes, width] blocks.  'two': the
         # reference's own statements -- MixedOp.set_arch_param_grad over the sampled pair, torch Adam on the alpha
         # parameters, rescale_updated_arch_param (search_vqa.py:330-334, mixed.py:179-208)
+        # fused_arch_update=True gives 'two' the same device-resident update: ArchAdam(mode='two'), one launch
+        # (ops.alpha_two_step) for those three statements; with 'full' the keyword changes nothing
+        self.fused_arch_update = bool(fused_arch_update) and arch_mode == 'two'
         if arch_mode == 'full':
             self.alpha_optim = ArchAdam(net, alpha_lr, alpha_betas, weight_decay=alpha_weight_decay)
+        elif self.fused_arch_update:
+            self.alpha_optim = ArchAdam(net, alpha_lr, alpha_betas, weight_decay=alpha_weight_decay, mode='two')
         else:
             net._flat_alphas()          # (the parameters' storage moves into the flat blocks before Adam sees them)
             self.alpha_optim = torch.optim.Adam(list(net.alpha_prob_parameters()), alpha_lr, betas=tuple(alpha_betas),
@@ -315,7 +348,7 @@ class SearchLoop:
             loss = self.loss_fn(net(inputs), target)
             loss.backward()
             red.reduce_alpha_gate_grads()
-            if self.arch_mode == 'two':
+            if self.arch_mode == 'two' and not self.fused_arch_update:
                 for m in net.redundant_modules:      # (the script's net.zero_grad() before backward, search_vqa.py:328)
                     m.alpha_prob.grad = None
                 net.set_arch_param_grad()

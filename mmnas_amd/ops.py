@@ -4,6 +4,7 @@ buffer the kernels touch is allocated here through torch's caching allocator and
 raw device pointer together with the current HIP stream.
 """
 import ctypes as C
+import math
 import os
 import threading
 
@@ -1627,6 +1628,82 @@ def alpha_full_step(prob, gate_grad, m, v, prob_grad, lr, betas, eps, step, weig
     L.check(L.lib().mmnas_alpha_full_step(L.fptr(prob), L.fptr(gate_grad), L.fptr(m), L.fptr(v), L.fptr(prob_grad),
                                           prob.shape[0], prob.shape[1], float(lr), float(betas[0]), float(betas[1]),
                                           float(eps), int(step), L.stream()))
+
+
+ALPHA_TWO_MAX_ROWS = 128      # mmnas_alpha_two_step carries the pairs in its kernel arguments
+
+
+def alpha_two_pair_grad(prob, gate_grad, idx):
+    """set_arch_param_grad of ALPHA_BINARY_MODE 'two' (mixed.py:179-186) for all rows at once, in torch: prob / gate_grad
+    [rows, width], idx [rows, 2] int64 (active, inactive).  Returns the [rows, width] gradient, zero outside the pairs."""
+    a = prob.gather(1, idx)
+    p = torch.softmax(a, dim=1)                       # over the pair only
+    gp = gate_grad.gather(1, idx) * p
+    return torch.zeros_like(prob).scatter_(1, idx, gp - p * gp.sum(dim=1, keepdim=True))
+
+
+def alpha_two_rescale(prob, old_pair, idx):
+    """rescale_updated_arch_param (mixed.py:200-208) for all rows at once, in place: `old_pair` [rows, 2] are the pairs'
+    logits before the optimizer step.  The offset is formed in float64, as the reference's math.log / math.exp do."""
+    new = prob.gather(1, idx)
+    off = torch.logsumexp(new.double(), dim=1, keepdim=True) - torch.logsumexp(old_pair.double(), dim=1, keepdim=True)
+    prob.scatter_(1, idx, (new.double() - off).to(prob.dtype))
+    return prob
+
+
+def _alpha_two_step_torch(prob, gate_grad, m, v, prob_grad, idx, lr, betas, eps, step, weight_decay):
+    """mmnas_alpha_two_step's arithmetic, statement for statement, in the tensors' own dtype."""
+    b1, b2 = float(betas[0]), float(betas[1])
+    c1 = 1.0 - b1 ** step
+    c2s = math.sqrt(1.0 - b2 ** step)
+    old = prob.gather(1, idx)
+    grad = alpha_two_pair_grad(prob, gate_grad, idx)
+    if prob_grad is not None:
+        prob_grad.copy_(grad)
+    valid = prob > float('-inf')                      # padding columns: logit, m and v stay as they are
+    if weight_decay:
+        grad = grad + weight_decay * torch.where(valid, prob, torch.zeros_like(prob))
+    mi = b1 * m + (1.0 - b1) * grad
+    vi = b2 * v + (1.0 - b2) * grad * grad
+    m.copy_(torch.where(valid, mi, m))
+    v.copy_(torch.where(valid, vi, v))
+    prob.copy_(torch.where(valid, prob - (lr / c1) * mi / (vi.sqrt() / c2s + eps), prob))
+    alpha_two_rescale(prob, old, idx)
+
+
+def alpha_two_step(prob, gate_grad, m, v, prob_grad, pairs, lr, betas, eps, step, weight_decay=0.0):
+    """All nodes' architecture update of ALPHA_BINARY_MODE 'two' (mixed.py:179-208, search_vqa.py:330-335) in one launch
+    (mmnas_alpha_two_step): the gradient over each node's sampled pair, torch Adam over the node's row, the pair's rescale.
+    prob / gate_grad / m / v [nodes, width] (padding columns of prob hold -inf), prob_grad the same or None, `pairs` one
+    (active, inactive) column pair per node (a host sequence: it travels in the kernel arguments, nothing is copied).
+    CUDA float32 tensors take the kernel; CPU tensors the same arithmetic in torch."""
+    rows, width = prob.shape
+    pairs = [(int(p[0]), int(p[1])) for p in pairs]
+    if len(pairs) != rows:
+        raise ValueError('alpha_two_step: %d pairs for %d rows' % (len(pairs), rows))
+    if rows > ALPHA_TWO_MAX_ROWS:
+        raise ValueError('alpha_two_step: %d rows, at most %d' % (rows, ALPHA_TWO_MAX_ROWS))
+    if int(step) < 1:
+        raise ValueError('alpha_two_step: step counts from 1, got %r' % (step,))
+    for r, (i, j) in enumerate(pairs):
+        if not (0 <= i < width and 0 <= j < width) or i == j:
+            raise ValueError('alpha_two_step: row %d: pair (%d, %d) must be two different columns of 0..%d' % (r, i, j, width - 1))
+    ts = [t for t in (prob, gate_grad, m, v, prob_grad) if t is not None]
+    if any(tuple(t.shape) != (rows, width) or t.device != prob.device for t in ts):
+        raise ValueError('alpha_two_step: prob, gate_grad, m, v and prob_grad share one [rows, width] shape and one device')
+    if rows == 0:
+        return
+    if prob.is_cuda:
+        arr = (C.c_int * (2 * rows))(*[c for p in pairs for c in p])
+        L.check(L.lib().mmnas_alpha_two_step(L.fptr(prob), L.fptr(gate_grad), L.fptr(m), L.fptr(v), L.fptr(prob_grad), rows, width,
+                                             arr, float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
+                                             int(step), L.stream()))
+        return
+    idx = torch.tensor(pairs, dtype=torch.int64)
+    if bool(torch.isinf(prob.gather(1, idx)).any()):      # (host tensors: the logits are at hand)
+        raise ValueError('alpha_two_step: a pair names a padding column')
+    with torch.no_grad():
+        _alpha_two_step_torch(prob, gate_grad, m, v, prob_grad, idx, float(lr), betas, float(eps), int(step), float(weight_decay))
 
 
 def row_is_zero(feature):
