@@ -847,6 +847,34 @@ int mmnas_itm_triplet_loss_fwd(const float* scores_pos, const float* scores_negc
 int mmnas_loss_grad_scale(const float* saved, const float* go, float* out, size_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The grounding head behind attfc_y (full_vgd.py:105-114; hygr_vgd.py carries the same lines) as one call per direction
+ * (csrc/vgdhead.hip; ops.GroundingHeadFn, opt-in through MMNAS_VGD_HEAD):
+ *     xy = proj_norm(x_pooled.unsqueeze(1) + yf);  scores = proj_scores(xy).squeeze(-1) [log_softmax over S];  reg = proj_reg(xy)
+ * with the LayerNorm of modules.py:44-56 (unbiased std, eps added to the std).  yf [B,S,F] is the attfc_y output, xp [B,F] the
+ * attflat_x output, ln_a / ln_b [F], Ws [1,F], bs [1], Wr [4,F], br [4].
+ *   mmnas_vgd_head_supported(S, F) (host only): 1 <= S <= 1024, 8 <= F <= 2048, F % 4 == 0.  Also 1 <= B <= 32768.
+ *   mmnas_vgd_head_fwd: scores [B,S], reg [B,S,4]; mean, rstd [B,S] (nullable together: nothing is saved) = the row mean and
+ *     1 / (std + eps) of xp + yf.  One launch, one workgroup per sample: each row is read once, the five projections are taken
+ *     from the normalised row in registers, the log_softmax runs over the sample's scores in LDS.
+ *   mmnas_vgd_head_bwd: dscores [B,S], dreg [B,S,4] -> dyf [B,S,F], dxp [B,F] = sum of dyf over S, dln_a, dln_b [F], dWs [1,F],
+ *     dbs [1], dWr [4,F], dbr [4]: every output is WRITTEN, not accumulated.  scores = the forward's output (read when
+ *     log_softmax; else nullable).  The normalised row is recomputed from yf, xp, mean and rstd.  ws: mmnas_vgd_head_bwd_ws_floats
+ *     (B, S, F) floats (host only; 0 outside the supported range): per-workgroup partials of dxp and of the parameter gradients,
+ *     added in a fixed order by a second small launch of the same call.  No floating-point atomics: bit-identical from call to
+ *     call.
+ * yf, xp, ln_a, ln_b, Ws, Wr, reg, dreg, dyf and ws are 16-byte aligned, else MMNAS_E_ARG; an unsupported shape: MMNAS_E_SHAPE.
+ * ------------------------------------------------------------------------------------------ */
+int mmnas_vgd_head_supported(int S, int F);
+size_t mmnas_vgd_head_bwd_ws_floats(int B, int S, int F);
+int mmnas_vgd_head_fwd(const float* yf, const float* xp, const float* ln_a, const float* ln_b, const float* Ws, const float* bs,
+                       const float* Wr, const float* br, float* scores, float* reg, float* mean, float* rstd, int B, int S, int F,
+                       float eps, int log_softmax, void* stream);
+int mmnas_vgd_head_bwd(const float* dscores, const float* dreg, const float* yf, const float* xp, const float* ln_a,
+                       const float* ln_b, const float* Ws, const float* Wr, const float* scores, const float* mean,
+                       const float* rstd, float* dyf, float* dxp, float* dln_a, float* dln_b, float* dWs, float* dbs, float* dWr,
+                       float* dbr, float* ws, int B, int S, int F, float eps, int log_softmax, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement aid (bench.py roofline): while enabled, every kernel launch of the classes below is
  * bracketed by HIP events recorded on the stream it is launched on and tagged with its ALGORITHMIC
  * flops / bytes; mmnas_prof_collect() synchronises the events, sums per class and resets.

@@ -227,6 +227,10 @@ SYMBOLS = {
     'mmnas_vgd_loss_fwd': (_i, [_fp] * 6 + [_i] * 6 + [C.c_double, C.c_double] + [_fp] * 5),
     'mmnas_itm_triplet_loss_fwd': (_i, [_fp, _fp, _fp, C.c_long, _i, _f, _i, _fp, _fp, _fp]),
     'mmnas_loss_grad_scale': (_i, [_fp, _fp, _fp, _sz, _fp]),
+    'mmnas_vgd_head_supported': (_i, [_i, _i]),
+    'mmnas_vgd_head_bwd_ws_floats': (_sz, [_i, _i, _i]),
+    'mmnas_vgd_head_fwd': (_i, [_fp] * 12 + [_i, _i, _i, _f, _i, _fp]),
+    'mmnas_vgd_head_bwd': (_i, [_fp] * 20 + [_i, _i, _i, _f, _i, _fp]),
     'mmnas_att_op_plan': (_i, [C.POINTER(AttOp), C.POINTER(Plan)]),
     'mmnas_att_op_fwd': (_i, [C.POINTER(AttOp), _fp]),
     'mmnas_att_op_bwd': (_i, [C.POINTER(AttOp), _fp]),

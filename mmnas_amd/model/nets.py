@@ -386,6 +386,10 @@ class _Net(nn.Module):
         x_out = self.attflat_x(x_out, x_mask)
         if self.TASK == 'vgd':  # per-object scores + box regression (full_vgd.py:105-114)
             y_out = ops.linear(y_out, self.attfc_y.weight, self.attfc_y.bias)
+            if ops.vgd_head_enabled() and y_out.is_cuda:   # opt-in (MMNAS_VGD_HEAD): everything below as one call per direction
+                return ops.grounding_head(y_out, x_out, self.proj_norm.a_2, self.proj_norm.b_2, self.proj_norm.eps,
+                                          self.proj_scores.weight, self.proj_scores.bias, self.proj_reg.weight,
+                                          self.proj_reg.bias, log_softmax=C.SCORES_LOSS == 'kld')
             xy = self.proj_norm(x_out.unsqueeze(1) + y_out)
             scores = ops.linear(xy, self.proj_scores.weight, self.proj_scores.bias).squeeze(-1)
             if C.SCORES_LOSS == 'kld':

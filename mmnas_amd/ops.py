@@ -646,6 +646,102 @@ def layer_norm(x, a, b, eps=1e-6):
     return LayerNormFn.apply(x, a, b, eps)
 
 
+# ------------------------------------------------------------------------------------------
+# Grounding head (full_vgd.py:105-114, the same lines in hygr_vgd.py): everything behind attfc_y -- the broadcast add of the
+# pooled language vector, proj_norm, proj_scores, proj_reg and the 'kld' mode's log_softmax over the regions -- as one native
+# call per direction (csrc/vgdhead.hip) instead of five autograd nodes that each stream a [B,S,F] tensor.  Nothing of that size
+# is written forward; the backward recomputes the normalised row from the saved attfc_y output and two statistics per row.
+# Opt-in: MMNAS_VGD_HEAD=1 (or set_vgd_head(True)) makes the VGD branch of the nets call it.  Off by default.
+# ------------------------------------------------------------------------------------------
+_vgd_head = [None]
+
+
+def vgd_head_enabled():
+    if _vgd_head[0] is None:
+        _vgd_head[0] = os.environ.get('MMNAS_VGD_HEAD', '0') == '1'
+    return _vgd_head[0]
+
+
+def set_vgd_head(on):
+    """Switch the fused grounding head of the VGD nets on / off (returns the previous setting)."""
+    prev = vgd_head_enabled()
+    _vgd_head[0] = bool(on)
+    return prev
+
+
+def _f32c16(t):
+    """Contiguous float32 and 16-byte aligned (a parameter that is a view into a flat buffer may start anywhere)."""
+    t = _f32c(t)
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+class GroundingHeadFn(torch.autograd.Function):
+    """(scores, reg) of the grounding head; every gradient goes back to autograd as a tensor."""
+
+    @staticmethod
+    def forward(ctx, yf, xp, ln_a, ln_b, eps, Ws, bs, Wr, br, log_softmax, save=True):
+        yf, xp, ln_a, ln_b, Ws, Wr = (_f32c16(t) for t in (yf, xp, ln_a, ln_b, Ws, Wr))
+        bs, br = _f32c(bs), _f32c(br)
+        B, S, F = yf.shape
+        dev = yf.device
+        scores = torch.empty(B, S, dtype=torch.float32, device=dev)
+        reg = torch.empty(B, S, 4, dtype=torch.float32, device=dev)
+        # (needs_input_grad ignores the grad mode, and forward always runs with it off: the caller passes `save`)
+        stats = torch.empty(2, B, S, dtype=torch.float32, device=dev) if save and any(ctx.needs_input_grad) else None
+        L.check(L.lib().mmnas_vgd_head_fwd(L.fptr(yf), L.fptr(xp), L.fptr(ln_a), L.fptr(ln_b), L.fptr(Ws), L.fptr(bs), L.fptr(Wr),
+                                           L.fptr(br), L.fptr(scores), L.fptr(reg), L.fptr(stats[0] if stats is not None else None),
+                                           L.fptr(stats[1] if stats is not None else None), B, S, F, eps, int(log_softmax), L.stream()))
+        if stats is not None:
+            ctx.save_for_backward(yf, xp, ln_a, ln_b, Ws, Wr, scores if log_softmax else None, stats)
+        ctx.eps, ctx.log_softmax = eps, bool(log_softmax)
+        return scores, reg
+
+    @staticmethod
+    def backward(ctx, dscores, dreg):
+        yf, xp, ln_a, ln_b, Ws, Wr, scores, stats = ctx.saved_tensors
+        B, S, F = yf.shape
+        dev = yf.device
+        # (an output the loss does not use arrives as zeros: autograd materialises it)
+        dscores, dreg = _f32c(dscores), _f32c16(dreg)
+        dyf = torch.empty_like(yf)
+        sizes = [B * F, F, F, F, 4 * F, 1, 4]
+        dxp, da, db, dWs, dWr, dbs, dbr = torch.split(torch.empty(sum(sizes), dtype=torch.float32, device=dev), sizes)
+        ws = torch.empty(L.lib().mmnas_vgd_head_bwd_ws_floats(B, S, F), dtype=torch.float32, device=dev)
+        L.check(L.lib().mmnas_vgd_head_bwd(L.fptr(dscores), L.fptr(dreg), L.fptr(yf), L.fptr(xp), L.fptr(ln_a), L.fptr(ln_b),
+                                           L.fptr(Ws), L.fptr(Wr), L.fptr(scores), L.fptr(stats[0]), L.fptr(stats[1]), L.fptr(dyf),
+                                           L.fptr(dxp), L.fptr(da), L.fptr(db), L.fptr(dWs), L.fptr(dbs), L.fptr(dWr), L.fptr(dbr),
+                                           L.fptr(ws), B, S, F, ctx.eps, int(ctx.log_softmax), L.stream()))
+        return dyf, dxp.view(B, F), da, db, None, dWs.view(1, F), dbs, dWr.view(4, F), dbr, None, None
+
+
+def _grounding_head_torch(yf, xp, ln_a, ln_b, eps, w_scores, b_scores, w_reg, b_reg, log_softmax):
+    """The reference's statements (full_vgd.py:105-114 with the LayerNorm of modules.py:44-56)."""
+    xy = xp.unsqueeze(1) + yf
+    mean = xy.mean(-1, keepdim=True)
+    std = xy.std(-1, keepdim=True)
+    xy = ln_a * (xy - mean) / (std + eps) + ln_b
+    scores = torch.nn.functional.linear(xy, w_scores, b_scores).squeeze(-1)
+    if log_softmax:
+        scores = torch.nn.functional.log_softmax(scores, dim=-1)
+    return scores, torch.nn.functional.linear(xy, w_reg, b_reg)
+
+
+def grounding_head(yf, xp, ln_a, ln_b, eps, w_scores, b_scores, w_reg, b_reg, log_softmax=True):
+    """yf [B,S,F] (the attfc_y output), xp [B,F] (the attflat_x output), ln_a / ln_b [F], w_scores [1,F], b_scores [1], w_reg [4,F],
+    b_reg [4] -> (scores [B,S], reg [B,S,4]).  float32 HIP tensors inside mmnas_vgd_head_supported's range run GroundingHeadFn;
+    CPU tensors, other dtypes and other shapes take the torch composition of the same statements."""
+    ts = (yf, xp, ln_a, ln_b, w_scores, b_scores, w_reg, b_reg)
+    native = yf.dim() == 3 and all(t.is_cuda and t.dtype == torch.float32 for t in ts)
+    if native:
+        B, S, F = yf.shape
+        native = (1 <= B <= 32768 and bool(L.lib().mmnas_vgd_head_supported(S, F))
+                  and [tuple(t.shape) for t in ts[1:]] == [(B, F), (F,), (F,), (1, F), (1,), (4, F), (4,)])
+    if not native:
+        return _grounding_head_torch(yf, xp, ln_a, ln_b, eps, w_scores, b_scores, w_reg, b_reg, log_softmax)
+    return GroundingHeadFn.apply(yf, xp, ln_a, ln_b, float(eps), w_scores, b_scores, w_reg, b_reg, bool(log_softmax),
+                                 torch.is_grad_enabled())
+
+
 class EltwiseFn(torch.autograd.Function):
     """kind: 0 zero (modules.py:96-101), 1 relu, 2 leaky-relu, 3 gelu-tanh (modules.py:104-109)."""
 
