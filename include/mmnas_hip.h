@@ -50,6 +50,20 @@ enum {
 int mmnas_abi_version(void);
 const char* mmnas_last_error(void);
 
+/* Runtime switches: every MMNAS_* environment variable the library reads is one row of one table (csrc/switches.h;
+ * docs/SWITCHES.md).  Row i of 0..count-1: the variable's name, a one-line description that starts with "[kind, read policy]",
+ * the default, the value the library runs with and where that value comes from.  Reading a row caches nothing: a switch that
+ * is read once and has not been read yet reports what a read at this moment would give, with MMNAS_SWITCH_UNREAD added to the
+ * source.  Any output pointer may be NULL; the strings are static.  Host only. */
+enum {
+  MMNAS_SWITCH_DEFAULT = 0,   /* the variable is unset (or empty) */
+  MMNAS_SWITCH_ENV = 1,       /* from the environment */
+  MMNAS_SWITCH_SET = 2,       /* installed by a mmnas_set_* call */
+  MMNAS_SWITCH_UNREAD = 4     /* flag: not read yet, a later change of the environment still counts */
+};
+int mmnas_switch_count(void);
+int mmnas_switch_info(int i, const char** name, const char** help, int* dflt, int* value, int* source);
+
 /* ------------------------------------------------------------------------------------------
  * Dropout generator.  nn.Dropout sites of the reference (modules.py:22,135-137,176,256,347)
  * draw from ATen's Philox stream; ours is counter-based: keep(idx) is a pure function of

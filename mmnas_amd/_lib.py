@@ -9,8 +9,10 @@ import os
 
 import torch
 
+from . import switches
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('MMNAS_LIB_PATH') or os.path.join(_HERE, 'lib', 'libmmnas_hip.so')   # (override: tuning builds)
+LIB_PATH = os.environ.get(switches.LIB_PATH.name) or os.path.join(_HERE, 'lib', 'libmmnas_hip.so')   # (override: tuning builds)
 
 log = logging.getLogger('mmnas_amd')
 
@@ -150,6 +152,8 @@ _i, _f, _u32, _u64, _sz = C.c_int, C.c_float, C.c_uint32, C.c_uint64, C.c_size_t
 SYMBOLS = {
     'mmnas_abi_version': (_i, []),
     'mmnas_last_error': (C.c_char_p, []),
+    'mmnas_switch_count': (_i, []),
+    'mmnas_switch_info': (_i, [_i, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)] + [C.POINTER(_i)] * 3),
     'mmnas_dropout_mask': (_i, [_fp, _sz, _f, _u64, _u32, _fp]),
     'mmnas_gemm': (_i, [C.POINTER(GemmDesc), _fp]),
     'mmnas_split_planes': (_i, [_fp, _fp, _sz, _fp]),

@@ -1002,10 +1002,7 @@ static int fill(const mmnas_mha_desc* d, MhaK& k, bool bwd) {
   return MMNAS_OK;
 }
 
-static int mha_nw() {
-  const char* e = getenv("MMNAS_MHA_NW");
-  return (e && atoi(e) == 2) ? 2 : 4;   // measured: 4-wave groups are 7-15 % faster (K/V tiles loaded half as often)
-}
+static int mha_nw() { return sw::mha_nw.get() == 2 ? 2 : 4; }   // measured: 4-wave groups are 7-15 % faster (K/V tiles loaded half as often)
 
 template <int DHC>
 static void launch_fwd(const MhaK& k, hipStream_t st) {
@@ -1053,7 +1050,7 @@ int mha_core_fwd_pair(const mmnas_mha_desc* d0, const mmnas_mha_desc* d1, hipStr
   int rc = fill(d0, k0, false);
   if (rc) return rc;
   if ((rc = fill(d1, k1, false))) return rc;
-  static const int on = [] { const char* e = getenv("MMNAS_MHA_PAIR"); return !(e && e[0] == '0'); }();
+  const bool on = sw::mha_pair.get() != 0;
   const int nkc = cdiv(k0.Sk, 32);
   const bool same = on && k0.B == k1.B && k0.H == k1.H && k0.Sq == k1.Sq && k0.Sk == k1.Sk && k0.dh == 64 && k1.dh == 64 &&
                     nkc > 2 && nkc <= 4 && k0.Sq > 64 && mha_nw() == 4 && !k0.qoff == !k1.qoff && !k0.koff == !k1.koff;
@@ -1143,7 +1140,7 @@ extern "C" int mmnas_mha_core_bwd(const mmnas_mha_desc* d, void* stream) {
   const double bhqk = (double)k.B * k.H * k.Sq * k.Sk;
   ProfScope ps(MMNAS_K_MHA_BWD, 10.0 * bhqk * k.dh,
                4.0 * ((double)k.B * k.H * k.dh * (4.0 * k.Sq + 4.0 * k.Sk) + (k.biasT ? 2.0 * bhqk : 0.0)), st);
-  static const bool fused_on = !(getenv("MMNAS_MHA_BWD_FUSED") && getenv("MMNAS_MHA_BWD_FUSED")[0] == '0');
+  const bool fused_on = sw::mha_bwd_fused.get() != 0;
   const bool packed = k.qoff || k.koff;
   if (packed) MMNAS_REQUIRE((((uintptr_t)k.dK | (uintptr_t)k.dV) & 15) == 0, MMNAS_E_ARG, "mha_bwd: dK / dV alignment (packed rows run the fused kernel only)");
   if ((fused_on || packed) && k.dh == 64 && k.Sq <= 128 && k.Sk <= 128 && (((uintptr_t)k.dK | (uintptr_t)k.dV) & 15) == 0) {

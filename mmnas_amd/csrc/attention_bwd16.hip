@@ -626,17 +626,14 @@ static bool fwd16_fill(MhaF16K& k, int B, int H, int Sq, int Sk, int ldq, int ld
   k.qoff = qoff; k.koff = koff;
   return true;
 }
-static bool fwd16_on() {
-  static const int on = [] { const char* e = getenv("MMNAS_MHA_FWD_B16"); return (e && e[0] == '0') ? 0 : 1; }();
-  return on != 0;
-}
+static bool fwd16_on() { return sw::mha_fwd_b16.get() != 0; }
 
 bool mha_fwd_b16_launch(int B, int H, int Sq, int Sk, int ldq, int ldk, int ldv, int ldo, const float* Q, const float* K, const float* V,
                         const uint8_t* mask, const float* biasT, float* O, float* stats, DropCfg drop, float scale, const int* qoff,
                         const int* koff, hipStream_t st) {
   MhaF16K k;
   if (!fwd16_on() || !fwd16_fill(k, B, H, Sq, Sk, ldq, ldk, ldv, ldo, Q, K, V, mask, biasT, O, stats, drop, scale, qoff, koff)) return false;
-  static const int two_from = [] { const char* e = getenv("MMNAS_MHA_FWD_B16_TWO"); return e && e[0] ? atoi(e) : 320; }();
+  const int two_from = sw::mha_fwd_b16_two.get();
   if ((long)B * H > two_from) MMNAS_LAUNCH(mha_fwd_b16_two_kernel, dim3(H, B), dim3(256), 0, st, k, k, H);   // more than one round: two per CU
   else MMNAS_LAUNCH(mha_fwd_b16_kernel, dim3(H, B), dim3(256), 0, st, k);
   return true;
@@ -658,8 +655,7 @@ bool mha_fwd_b16_pair(int B, int H, int Sq, int Sk, int ld, const float* const* 
 bool mha_bwd_b16_launch(int B, int H, int Sq, int Sk, int ldq, int ldk, int ldv, int ldo, const float* Q, const float* K, const float* V,
                         const float* O, const float* dO, const uint8_t* mask, const float* biasT, const float* stats, float* dQ, float* dK,
                         float* dV, float* dbiasT, DropCfg drop, float scale, const int* qoff, const int* koff, hipStream_t st) {
-  static const int on = [] { const char* e = getenv("MMNAS_MHA_BWD_B16"); return (e && e[0] == '0') ? 0 : 1; }();
-  if (!on || Sq > 128 || Sk > 128 || Sk <= 64) return false;   // (few keys: waves without keys would idle -- the fp32 kernel's small instantiations stay)
+  if (!sw::mha_bwd_b16.get() || Sq > 128 || Sk > 128 || Sk <= 64) return false;   // (few keys: waves without keys would idle -- the fp32 kernel's small instantiations stay)
   if ((((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V | (uintptr_t)O | (uintptr_t)dO | (uintptr_t)dQ | (uintptr_t)dK | (uintptr_t)dV) & 15) != 0) return false;
   if ((ldq | ldk | ldv | ldo) % 4 != 0) return false;
   MhaB16K k;

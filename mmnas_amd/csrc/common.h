@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include "../../include/mmnas_hip.h"
 #include "rng.h"
+#include "switches.h"
 
 namespace mmnas {
 

@@ -1110,45 +1110,31 @@ __global__ void __launch_bounds__(256, NS ? MMNAS_OCC_NS : MMNAS_OCC64) gemm_pai
 
 // ---- stream-K workspace: partial-tile slots + arrival counters, one per stream (launches on one stream
 //      are ordered, so they can share it; two streams must not) ----
-static int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e && e[0] ? atoi(e) : dflt;
-}
-
-// Tuning / test knobs, read from the environment once (mmnas_gemm_reload_tuning() re-reads them):
-//   MMNAS_GEMM_TILE=64|128 force the tile shape      MMNAS_GEMM_GENERIC=1 force the guarded-load path
-//   MMNAS_GEMM_SK=0|1|2    stream-K / split-K never, automatic, always
-//   MMNAS_GEMM_WGS=n       co-resident workgroup budget (default 1024 for 64^2 tiles, 512 for 128^2)
-//   MMNAS_GEMM_MIN_UNITS=n fewest K-tiles a workgroup is given (default 4)
-//   MMNAS_GEMM_GM=n        row-panels per tile-order block (default 8)     MMNAS_GEMM_XCD=0 identity workgroup mapping
-//   MMNAS_GEMM_SPLIT=0|1|3|6 products on the fp32 MFMA / as 1 (bf16-rounded operands: reduced precision) / 3 / 6 (default: fp32-grade)
-//                          bf16 MFMA products of split operands
-//   MMNAS_GEMM_PAIR=0      mmnas_gemm_pair launches its two products separately
-//   MMNAS_GEMM_LEAN=0|1|2|3 bit 0: NT / NN products, bit 1: split-K TN products on the lean kernels (default 3)
-//   MMNAS_GEMM_PF=1|2      K-tiles of operand loads in flight ahead of the MFMA block (64^2 fp32 buffer-load path)
+// Tuning / test knobs (the MMNAS_GEMM_* rows of switches.h), read from the environment once; mmnas_gemm_reload_tuning()
+// re-reads them.
 struct Tuning { int tile, generic, sk, wgs, min_units, gm, xcd, split, pair, split_slots, split_p, pf, wide_min, split_minwg, hyb_t, lean, lean_maxb; bool loaded; };
 static Tuning g_tune = {0, 0, 1, 0, 4, 0, 1, 3, 1, 0, 24, 2, 200, 256, 16, 3, 8 << 20, false};
 static void load_tuning() {
-  g_tune.tile = env_int("MMNAS_GEMM_TILE", 0);
-  g_tune.generic = getenv("MMNAS_GEMM_GENERIC") != nullptr;
-  g_tune.sk = env_int("MMNAS_GEMM_SK", 1);
-  g_tune.wgs = env_int("MMNAS_GEMM_WGS", 0);
-  g_tune.min_units = env_int("MMNAS_GEMM_MIN_UNITS", 4);
+  g_tune.tile = sw::gemm_tile.reload();
+  g_tune.generic = sw::gemm_generic.reload();
+  g_tune.sk = sw::gemm_sk.reload();
+  g_tune.wgs = sw::gemm_wgs.reload();
+  g_tune.min_units = sw::gemm_min_units.reload();
   if (g_tune.min_units < 1) g_tune.min_units = 1;
-  g_tune.gm = env_int("MMNAS_GEMM_GM", 0);
-  g_tune.xcd = env_int("MMNAS_GEMM_XCD", 1);
-  const int sp = env_int("MMNAS_GEMM_SPLIT", 6);
+  g_tune.gm = sw::gemm_gm.reload();
+  g_tune.xcd = sw::gemm_xcd.reload();
+  const int sp = sw::gemm_split.reload();
   g_tune.split = sp == 3 ? 2 : (sp == 6 ? 3 : (sp == 1 ? 1 : 0));   // number of bf16 parts per operand
-  g_tune.pair = env_int("MMNAS_GEMM_PAIR", 1);
-  g_tune.split_slots = env_int("MMNAS_GEMM_SPLIT_SLOTS", 0);
-  g_tune.split_p = env_int("MMNAS_GEMM_SPLIT_P", 24);           // K-tiles per split-K piece
+  g_tune.pair = sw::gemm_pair.reload();
+  g_tune.split_slots = sw::gemm_split_slots.reload();
+  g_tune.split_p = sw::gemm_split_p.reload();           // K-tiles per split-K piece
   if (g_tune.split_p < 1) g_tune.split_p = 1;
-  g_tune.split_minwg = env_int("MMNAS_GEMM_SPLIT_MINWG", 256);  // fewest split-K pieces in total (x tiles) when pieces of split_p would be fewer
-  g_tune.pf = env_int("MMNAS_GEMM_PF", 2) == 1 ? 1 : 2;            // register stages of operand prefetch (64^2 fp32 path)
-  g_tune.hyb_t = env_int("MMNAS_GEMM_HYB_T", 16);                // fewest K-tiles per output tile for the whole-tiles + streamed-tail hybrid
-  g_tune.wide_min = env_int("MMNAS_GEMM_WIDE_MIN", 200);         // fewest 128x64 tiles for that shape to be chosen
-  g_tune.lean = env_int("MMNAS_GEMM_LEAN", 3);                   // bit 0: lean NT / NN kernels (short set-up, 16-byte epilogue rows); bit 1: lean TN
-  g_tune.lean_maxb = env_int("MMNAS_GEMM_LEAN_MAXB", 8 << 20);   // largest B matrix (bytes) the lean tile order is used for
+  g_tune.split_minwg = sw::gemm_split_minwg.reload();
+  g_tune.pf = sw::gemm_pf.reload() == 1 ? 1 : 2;        // register stages of operand prefetch (64^2 fp32 path)
+  g_tune.hyb_t = sw::gemm_hyb_t.reload();
+  g_tune.wide_min = sw::gemm_wide_min.reload();
+  g_tune.lean = sw::gemm_lean.reload();
+  g_tune.lean_maxb = sw::gemm_lean_maxb.reload();
   g_tune.loaded = true;
 }
 
@@ -1660,7 +1646,7 @@ extern "C" int mmnas_lstm_fwd(const float* x_tm, const float* Wih, const float* 
     d.ldres = 4 * H; d.alpha = 1.f; d.gate_scale = 1.f; d.split_k = 1;
     d.g[0].M = B; d.g[0].A[0] = Hall + t * bh; d.g[0].B[0] = Whh; d.g[0].C = Hall + (t + 1) * bh; d.g[0].residual = xp + t * bg;
     GemmPlan pl;
-    if ((rc = lstm_step_plan(pl, d, st, "lstm_fwd", env_int("MMNAS_LSTM_FWD_P", 0)))) return rc;
+    if ((rc = lstm_step_plan(pl, d, st, "lstm_fwd", sw::lstm_fwd_p.get()))) return rc;
     pl.k.lg_cprev = Call + t * bh; pl.k.lg_cout = Call + (t + 1) * bh; pl.k.lg_gates = Gall + t * bg;
     pl.k.lg_h2 = out + (size_t)t * H; pl.k.lg_ldh2 = T * H;
     ProfScope ps(MMNAS_K_GEMM, pl.flops, pl.bytes, st, pl.tag);
@@ -1684,7 +1670,7 @@ extern "C" int mmnas_lstm_bwd(const float* dout, const float* Whh, const float* 
     d.g[0].M = B; d.g[0].A[0] = DG + (t + 1) * bg; d.g[0].B[0] = Whh; d.g[0].C = scratch; d.g[0].residual = dout + (size_t)t * H;
     GemmPlan pl;
     int rc;
-    if ((rc = lstm_step_plan(pl, d, st, "lstm_bwd", env_int("MMNAS_LSTM_BWD_P", 8)))) return rc;
+    if ((rc = lstm_step_plan(pl, d, st, "lstm_bwd", sw::lstm_bwd_p.get()))) return rc;
     pl.k.lg_act = Gall + t * bg; pl.k.lg_c = Call + (t + 1) * bh; pl.k.lg_cprev = Call + t * bh;
     pl.k.lg_dc = dc; pl.k.lg_gates = DG + t * bg;
     ProfScope ps(MMNAS_K_GEMM, pl.flops, pl.bytes, st, pl.tag);

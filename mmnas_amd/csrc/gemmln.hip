@@ -252,23 +252,17 @@ __global__ void __launch_bounds__(LN_NT, 1) gemm_ln_kernel(const GemmLnK p) {
   }
 }
 
-static int g_gemm_ln = -1;   // -1: not read yet (MMNAS_GEMM_LN, default 0: opt-in); mmnas_set_gemm_ln() overrides
-static int g_gemm_ln_minm = 2048;
-static int g_gemm_ln_maxk = 256;
+// MMNAS_GEMM_LN (default 0: opt-in; mmnas_set_gemm_ln() overrides) and its two tuning rows, read together
 static bool gemm_ln_on() {
-  if (g_gemm_ln < 0) {
-    const char* e = getenv("MMNAS_GEMM_LN");
+  if (!sw::gemm_ln.state) {
     // OPT-IN (round 6, profiles/r06_ab.txt): on one box, alternating runs, the supernet step is 4.556 / 4.549 / 4.564 ms with
     // the panel kernel and 4.561 / 4.551 / 4.554 ms without -- neutral (the launch it removes is paid back by a product that
     // runs 3.7 us longer inside the step than the 64^2 tiling with 2-3 workgroups per CU); the ragged stream loses 0.03 ms
     // (3900 valid rows = 122 panels on 256 CUs).  VERDICT r5 item 1(b): "if it measures neutral, keep it opt-in".
-    g_gemm_ln = (e && e[0] == '1') ? 1 : 0;
-    const char* m = getenv("MMNAS_GEMM_LN_MINM");   // products with fewer rows keep the two-launch form (tuning)
-    g_gemm_ln_minm = m && m[0] ? atoi(m) : 2048;
-    const char* k = getenv("MMNAS_GEMM_LN_MAXK");
-    g_gemm_ln_maxk = k && k[0] ? atoi(k) : 256;    // (measured, tools/gemm_ln_bench.py: -3.4 us at K = 256, +-0.5 at 512, +1.5 at 1024)    // (896 rows = 28 panels on 256 CUs: the tiled product + LayerNorm win there)
+    sw::gemm_ln_minm.get();   // products with fewer rows keep the two-launch form (896 rows = 28 panels on 256 CUs: the tiled product + LayerNorm win there)
+    sw::gemm_ln_maxk.get();   // (measured, tools/gemm_ln_bench.py: -3.4 us at K = 256, +-0.5 at 512, +1.5 at 1024)
   }
-  return g_gemm_ln != 0;
+  return sw::gemm_ln.get() != 0;
 }
 
 // The product of *d (the merge / last FFN projection as the operators describe it) qualifies for the panel kernel:
@@ -280,7 +274,7 @@ bool gemm_ln_applies(const mmnas_gemm_desc* d) {
   if (d->relu || d->accumulate || d->split_k > 1 || d->alpha != 1.f) return false;
   if (d->b_planes && d->ldb % 8 != 0) return false;
   const mmnas_gemm_group& g = d->g[0];
-  if (g.gate || g.colsum || g.M < 1 || g.M < g_gemm_ln_minm || d->K > g_gemm_ln_maxk) return false;
+  if (g.gate || g.colsum || g.M < 1 || g.M < sw::gemm_ln_minm.get() || d->K > sw::gemm_ln_maxk.get()) return false;
   if (g.residual && d->ldres % 4 != 0) return false;
   if (((uintptr_t)g.A[0] | (uintptr_t)g.B[0] | (uintptr_t)g.C | (uintptr_t)g.residual | (uintptr_t)g.bias) & 15) return false;
   if ((double)g.M * d->lda * 4.0 >= 4294967296.0 || (double)g.M * d->ldc * 4.0 >= 4294967296.0) return false;
@@ -315,10 +309,8 @@ int gemm_ln(const mmnas_gemm_desc* d, const float* ln_a, const float* ln_b, floa
 using namespace mmnas;
 
 extern "C" int mmnas_set_gemm_ln(int on) {
-  gemm_ln_on();
-  const int old = g_gemm_ln;
-  g_gemm_ln = on ? 1 : 0;
-  return old;
+  gemm_ln_on();   // (the tuning rows are read with the switch: the first read is here when this call comes first)
+  return sw::gemm_ln.set(on != 0);
 }
 
 extern "C" int mmnas_gemm_ln(const mmnas_gemm_desc* d, const float* ln_a, const float* ln_b, float* y, float eps, void* stream) {

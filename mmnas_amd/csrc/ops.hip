@@ -158,7 +158,7 @@ static int att_core_fwd(const mmnas_att_op* op, const AttLayout& L, void* stream
       // operators of a stream (relmulti.hip).  A row's bias does not depend on which other rows share its launch, so the
       // per-operator path and the chains produce the same bias BIT FOR BIT -- and with it the same logits.
       if (op->Sq == op->Sk && mmnas_rel_multi_supported(op->C, op->R, op->H) && (long)op->B * op->H * op->Sq * op->Sq < (1l << 31) &&
-          !(getenv("MMNAS_REL_FWD_VALU") && getenv("MMNAS_REL_FWD_VALU")[0] == '1')) {
+          !sw::rel_fwd_valu.get()) {
         mmnas_rel_multi q;
         memset(&q, 0, sizeof(q));
         q.B = op->B; q.S = op->Sq; q.C = op->C; q.R = op->R; q.H = op->H; q.n_ops = 1;
@@ -779,7 +779,7 @@ static SideCtx* side_ctx(hipStream_t main, bool create) {
     memset(&s, 0, sizeof(s));
     // lowest priority: when both streams have workgroups to dispatch, the data-gradient chain goes first
     int least = 0, greatest = 0;
-    const bool prio = !(getenv("MMNAS_SIDE_PRIO") && getenv("MMNAS_SIDE_PRIO")[0] == '0') &&
+    const bool prio = sw::side_prio.get() &&
                       hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest;
     if ((prio ? hipStreamCreateWithPriority(&s.side, hipStreamNonBlocking, least)
               : hipStreamCreateWithFlags(&s.side, hipStreamNonBlocking)) != hipSuccess) return nullptr;
@@ -805,23 +805,10 @@ static SideCtx* side_ctx(hipStream_t main, bool create) {
 // GEMM one of its three workgroups per CU meanwhile: in the trace the co-running kernels take 1.3-1.5x their solo time
 // (GEMM 26.6 -> 39.6 us, attention 22 -> 32 us), which returns what the overlap saves.  Off by default
 // (MMNAS_CHAIN_OVERLAP=1 enables it); kept because the fork / join structure is what a multi-stream caller needs.
-static int g_chain_overlap = -1;   // -1: not read yet (MMNAS_CHAIN_OVERLAP, default 0); mmnas_set_chain_overlap() overrides
-static bool chain_overlap_on() {
-  if (g_chain_overlap < 0) { const char* e = getenv("MMNAS_CHAIN_OVERLAP"); g_chain_overlap = (e && e[0] ? atoi(e) : 0) ? 1 : 0; }
-  return g_chain_overlap != 0;
-}
-static bool head_overlap_on() {
-  static const int on = [] { const char* e = getenv("MMNAS_HEAD_OVERLAP"); return e && e[0] ? atoi(e) : 0; }();
-  return on != 0;
-}
-static bool head_glimpse1_on() {   // MMNAS_HEAD_GLIMPSE1=0: the one-glimpse logit layer as GEMM launches (A/B, tests)
-  const char* e = getenv("MMNAS_HEAD_GLIMPSE1");
-  return !(e && e[0] == '0');
-}
-static bool head_projT_on() {   // MMNAS_HEAD_PROJT=0: the answer projection's gradients from the untransposed loss gradient
-  const char* e = getenv("MMNAS_HEAD_PROJT");
-  return !(e && e[0] == '0');
-}
+static bool chain_overlap_on() { return sw::chain_overlap.get() != 0; }   // mmnas_set_chain_overlap() overrides
+static bool head_overlap_on() { return sw::head_overlap.get() != 0; }
+static bool head_glimpse1_on() { return sw::head_glimpse1.get() != 0; }   // 0: the one-glimpse logit layer as GEMM launches (A/B, tests); read per call
+static bool head_projT_on() { return sw::head_projt.get() != 0; }         // 0: the answer projection's gradients from the untransposed loss gradient; read per call
 static int first_guided(const mmnas_chain* c) {
   for (int i = 0; i < c->n_ops; ++i)
     if (c->ops[i].kind == MMNAS_CHAIN_ATT && !(c->ops[i].att.flags & MMNAS_F_SELF)) return i;
@@ -837,11 +824,7 @@ static int ev_fork(hipStream_t from, hipStream_t to, hipEvent_t e) {
 
 
 // ---- relation bias of all lazy-handle relation operators of a stream in one launch per direction (relmulti.hip) ----
-static int g_rel_hoist = -1;   // -1: not read yet (MMNAS_REL_HOIST, default 1); mmnas_set_rel_hoist() overrides
-static bool rel_hoist_on() {
-  if (g_rel_hoist < 0) { const char* e = getenv("MMNAS_REL_HOIST"); g_rel_hoist = (e && e[0] ? atoi(e) : 1) ? 1 : 0; }
-  return g_rel_hoist != 0;
-}
+static bool rel_hoist_on() { return sw::rel_hoist.get() != 0; }   // default 1; mmnas_set_rel_hoist() overrides
 struct RelGroups {
   std::vector<mmnas_rel_multi> groups[2];      // [0]: the language stream's, [1]: the image stream's
   bool hoisted[MMNAS_CHAIN_MAX_OPS];
@@ -898,11 +881,7 @@ static int chain_rel_fwd(const RelGroups& G, hipStream_t st, int only = -1) {
 // on the side stream behind the decoder's first operator (every bias gradient exists) and joined at the end of the call,
 // while the encoder's backward runs on the caller's stream.  A bucket mark that covers the relation parameters is recorded
 // on the side stream behind the launch (the side stream waited for the caller's stream first: the event covers both).
-static int g_rel_overlap = -1;
-static bool rel_overlap_on() {
-  if (g_rel_overlap < 0) { const char* e = getenv("MMNAS_REL_OVERLAP"); g_rel_overlap = (e && e[0] ? atoi(e) : 0) ? 1 : 0; }
-  return g_rel_overlap != 0;
-}
+static bool rel_overlap_on() { return sw::rel_overlap.get() != 0; }
 static int chain_rel_bwd(const RelGroups& G, int stream_y, hipStream_t st) {
   for (const auto& g : G.groups[stream_y]) {
     MMNAS_REQUIRE(g.dWy && g.dby, MMNAS_E_ARG, "chain_bwd: relation operators without the stem layer's gradient sinks");
@@ -920,16 +899,8 @@ static int chain_rel_bwd(const RelGroups& G, int stream_y, hipStream_t st) {
 // then projects only its queries.  Backward: behind the LAST guided operator's backward (the first in chain order), the
 // key / value source gradients dxkv_n = dK_n Wk_n + dV_n Wv_n into per-operator buffers and dWk_n / dWv_n, 4 operators per
 // gradient-pair launch; one add_many launch sums the buffers (and the head's gradient) into the encoder's output gradient.
-static int g_node_lnb = -1;   // MMNAS_NODE_LNB, default 1: the sampled candidate's LayerNorm backward inside the node's mix kernel
-static bool node_lnb_on() {
-  if (g_node_lnb < 0) { const char* e = getenv("MMNAS_NODE_LNB"); g_node_lnb = (e && e[0] ? atoi(e) : 1) ? 1 : 0; }
-  return g_node_lnb != 0;
-}
-static int g_guided_hoist = -1;   // MMNAS_GUIDED_HOIST, default 1
-static bool guided_hoist_on() {
-  if (g_guided_hoist < 0) { const char* e = getenv("MMNAS_GUIDED_HOIST"); g_guided_hoist = (e && e[0] ? atoi(e) : 1) ? 1 : 0; }
-  return g_guided_hoist != 0;
-}
+static bool node_lnb_on() { return sw::node_lnb.get() != 0; }   // default 1: the sampled candidate's LayerNorm backward inside the node's mix kernel
+static bool guided_hoist_on() { return sw::guided_hoist.get() != 0; }   // default 1
 struct GuidedSet {
   int idx[MMNAS_CHAIN_MAX_OPS], n;
   bool hoisted[MMNAS_CHAIN_MAX_OPS];
@@ -1012,29 +983,10 @@ static int chain_guided_kv_bwd(const mmnas_chain* c, const ChainLayout& L, const
 
 }  // namespace mmnas
 
-extern "C" int mmnas_set_rel_overlap(int on) {
-  const int prev = mmnas::rel_overlap_on() ? 1 : 0;
-  mmnas::g_rel_overlap = on ? 1 : 0;
-  return prev;
-}
-
-extern "C" int mmnas_set_guided_hoist(int on) {
-  const int prev = mmnas::guided_hoist_on() ? 1 : 0;
-  mmnas::g_guided_hoist = on ? 1 : 0;
-  return prev;
-}
-
-extern "C" int mmnas_set_rel_hoist(int on) {
-  const int prev = mmnas::rel_hoist_on() ? 1 : 0;
-  mmnas::g_rel_hoist = on ? 1 : 0;
-  return prev;
-}
-
-extern "C" int mmnas_set_chain_overlap(int on) {
-  const int prev = mmnas::chain_overlap_on() ? 1 : 0;
-  mmnas::g_chain_overlap = on ? 1 : 0;
-  return prev;
-}
+extern "C" int mmnas_set_rel_overlap(int on) { return mmnas::sw::rel_overlap.set(on != 0); }
+extern "C" int mmnas_set_guided_hoist(int on) { return mmnas::sw::guided_hoist.set(on != 0); }
+extern "C" int mmnas_set_rel_hoist(int on) { return mmnas::sw::rel_hoist.set(on != 0); }
+extern "C" int mmnas_set_chain_overlap(int on) { return mmnas::sw::chain_overlap.set(on != 0); }
 
 extern "C" int mmnas_chain_plan(const mmnas_chain* c, size_t* arena_bytes) {
   int rc = chain_check(c, "chain_plan");
@@ -1458,7 +1410,7 @@ extern "C" int mmnas_chain_bwd(const mmnas_chain* c, void* stream) {
   // When the queued parameter-gradient work is released: MMNAS_SIDE_FLUSH=op -> behind every operator (it then competes
   // with the data-gradient chain for the CUs); default -> once behind the decoder and once behind the encoder, so it
   // fills the latency-bound tail of the backward pass (encoder on 896 rows, LSTM, stem) instead.
-  static const bool per_op = getenv("MMNAS_SIDE_FLUSH") && !strcmp(getenv("MMNAS_SIDE_FLUSH"), "op");
+  static const bool per_op = getenv(sw::side_flush.name) && !strcmp(getenv(sw::side_flush.name), "op");
   char* base = (char*)c->arena;
   const size_t ex = (size_t)c->B * c->Sx * c->d, ey = chain_rows_y(c) * c->d;
   float* dpre = (float*)(base + L.dpre);

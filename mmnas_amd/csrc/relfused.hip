@@ -823,7 +823,7 @@ static int rf_bwd_impl(const float* raw, const float* Wy, const float* by, const
   if (off) MMNAS_REQUIRE(toff && Sq == Sk && ntiles_ragged >= 0 && ntiles_ragged <= B * tpb, MMNAS_E_ARG,
                          "rel_fused_bwd: ragged batches need tile offsets, Sq == Sk and a tile count <= the dense one (%d vs %d)", ntiles_ragged, B * tpb);
   const int ntiles = off ? ntiles_ragged : B * tpb;
-  static const bool vpath = !(getenv("MMNAS_REL_BWD_VALU") && getenv("MMNAS_REL_BWD_VALU")[0] == '0');   // 0: the all-MFMA kernel (A/B runs)
+  const bool vpath = sw::rel_bwd_valu.get() != 0;   // 0: the all-MFMA kernel (A/B runs)
   const bool use_v = H <= 4 && vpath;
   const int grid = rf_grid(ntiles > 0 ? ntiles : 1, 2);
   hipStream_t st = (hipStream_t)stream;

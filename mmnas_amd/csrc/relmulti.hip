@@ -518,7 +518,7 @@ extern "C" int mmnas_rel_multi_fwd(const mmnas_rel_multi* m, void* stream) {
     RelMultiK k;
     memset(&k, 0, sizeof(k));
     k.raw = m->raw; k.B = m->B; k.S = m->S; k.C = m->C; k.H = m->H; k.off = m->off; k.toff = m->tile_off;
-    { static const int dbg = [] { const char* e = getenv("MMNAS_REL_MULTI_DBG"); return e && e[0] ? atoi(e) : 0; }(); k.dbg = dbg; }
+    k.dbg = sw::rel_multi_dbg.get();
     // rows: operator j of this launch holds rows j H .. j H + H - 1 (H divides 32: no operator straddles two row tiles)
     for (int j = 0; j < n; ++j) {
       MMNAS_REQUIRE(m->Wr[o0 + j] && m->br[o0 + j] && m->biasT[o0 + j], MMNAS_E_ARG, "rel_multi_fwd: operator %d: null pointer", o0 + j);
@@ -528,11 +528,11 @@ extern "C" int mmnas_rel_multi_fwd(const mmnas_rel_multi* m, void* stream) {
     for (int j = 0; j < n; ++j) { k.Wr[j] = m->Wr[o0 + j]; k.br[j] = m->br[o0 + j]; }
     k.nops = n; k.nrows = slots;
     const int nt = (slots + RM_ROWS - 1) / RM_ROWS;
-    static const int fwd_per_cu = [] { const char* e = getenv("MMNAS_REL_MULTI_WGS"); return e && e[0] ? atoi(e) : 3; }();   // (tuning: workgroups per CU)
+    const int fwd_per_cu = sw::rel_multi_wgs.get();   // (tuning: workgroups per CU)
     const int grid = rm_grid(ntiles, fwd_per_cu);
     const double ne = m->off ? 32.0 * ntiles : (double)m->B * SS;
     ProfScope ps(MMNAS_K_REL_FWD, 2.0 * ne * (RM_R * (m->C + 1) + (double)n * m->H * RM_R), 4.0 * ne * (m->C + n * m->H), st);
-    static const int yield = [] { const char* e = getenv("MMNAS_REL_MULTI_YIELD"); return e && e[0] ? atoi(e) : 0; }();
+    const int yield = sw::rel_multi_yield.get();
 #define RM_FWD(CC, NTT) do { if (yield == 1) MMNAS_LAUNCH((rel_multi_fwd_kernel<CC, NTT, 1>), dim3(grid), dim3(256), 0, st, k, ntiles, tpb, m->Wy, m->by); \
       else if (yield == 3) MMNAS_LAUNCH((rel_multi_fwd_kernel<CC, NTT, 3>), dim3(grid), dim3(256), 0, st, k, ntiles, tpb, m->Wy, m->by); \
       else MMNAS_LAUNCH((rel_multi_fwd_kernel<CC, NTT, 0>), dim3(grid), dim3(256), 0, st, k, ntiles, tpb, m->Wy, m->by); } while (0)
@@ -574,7 +574,7 @@ extern "C" int mmnas_rel_multi_bwd(const mmnas_rel_multi* m, void* stream) {
     const double ne = m->off ? 32.0 * ntiles : (double)m->B * SS;
     const double rows = (double)n * m->H;
     ProfScope ps(MMNAS_K_REL_BWD, 2.0 * ne * (2.0 * RM_R * (m->C + 1) + 3.0 * rows * RM_R), 4.0 * ne * (m->C + rows), st);
-    static const int yield = [] { const char* e = getenv("MMNAS_REL_MULTI_YIELD"); return e && e[0] ? atoi(e) : 0; }();
+    const int yield = sw::rel_multi_yield.get();
 #define RM_BWD(CC) do { if (yield == 1) MMNAS_LAUNCH((rel_multi_bwd_kernel<CC, 1>), dim3(grid), dim3(256), 0, st, k, ntiles, tpb, m->Wy, m->by); \
       else if (yield == 3) MMNAS_LAUNCH((rel_multi_bwd_kernel<CC, 3>), dim3(grid), dim3(256), 0, st, k, ntiles, tpb, m->Wy, m->by); \
       else MMNAS_LAUNCH((rel_multi_bwd_kernel<CC, 0>), dim3(grid), dim3(256), 0, st, k, ntiles, tpb, m->Wy, m->by); } while (0)

@@ -882,15 +882,7 @@ __global__ void __launch_bounds__(256, HS == 256 ? 1 : 2) ffn_small_fwd_kernel(c
 }
 
 
-static int env_on(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e && e[0] ? atoi(e) : dflt;
-}
-static int g_small_ops = -1;   // -1: not read yet
-static bool small_ops_on() {
-  if (g_small_ops < 0) g_small_ops = env_on("MMNAS_SMALL_OPS", 1) ? 1 : 0;
-  return g_small_ops != 0;
-}
+static bool small_ops_on() { return sw::small_ops.get() != 0; }
 
 // Does the short-sequence kernel take this operator?  (self-attention without relation bias, <= 16 rows per sample,
 // heads of 64, model width 256 or 512, at most 256 (sample, head) pairs; MMNAS_SMALL_OPS=0 switches the family off)
@@ -929,11 +921,7 @@ int sa_small_fwd(const mmnas_att_op* op, float* Q, float* K, float* V, float* at
   return check_launch("sa_small_fwd");
 }
 
-static int g_small_bwd = -1;
-static bool small_bwd_on() {
-  if (g_small_bwd < 0) g_small_bwd = env_on("MMNAS_SMALL_BWD", 1) ? 1 : 0;
-  return g_small_bwd != 0;
-}
+static bool small_bwd_on() { return sw::small_bwd.get() != 0; }
 
 // Does the one-launch backward take this operator?  (What the forward kernel takes -- either backward may follow either
 // forward, the saved block is the same -- and a LayerNorm partial row per sample must fit the operator's LayerNorm scratch.)
@@ -973,11 +961,8 @@ int sa_small_bwd(const mmnas_att_op* op, const float* Q, const float* K, const f
 
 // Does the one-launch FeedForward forward take this operator?  (two layers d -> 4d -> d with d = 256 and at most 1024 rows:
 // 4 workgroups per group of 16 rows, one round of <= 256)
-static int g_small_ffn = -1;
-static bool small_ffn_on() {     // default OFF: measured neutral against the three launches it replaces (see the header comment)
-  if (g_small_ffn < 0) g_small_ffn = env_on("MMNAS_SMALL_FFN", 0);      // 1: four slices of 256 hidden units; 2: eight of 128
-  return g_small_ffn != 0;
-}
+// default OFF: measured neutral against the three launches it replaces (see the header comment); 1: four slices of 256 hidden units; 2: eight of 128
+static bool small_ffn_on() { return sw::small_ffn.get() != 0; }
 bool ffn_small_applies(const mmnas_mlp_op* op) {
   if (!small_ops_on() || !small_ffn_on()) return false;
   return op->nl == 2 && op->dims[0] == 256 && op->dims[1] == 1024 && op->dims[2] == 256 && op->M <= 1024 && op->W[0] && op->W[1];
@@ -997,7 +982,7 @@ int ffn_small_fwd(const mmnas_mlp_op* op, float* h, float* z, hipStream_t st) {
   size_t wsf = 0; int ncnt = 0;
   int rc = sk_workspace(st, &k.part, &wsf, &k.cnt, &ncnt);
   if (rc) return rc;
-  const int nsl = g_small_ffn == 2 ? 8 : 4;
+  const int nsl = sw::small_ffn.get() == 2 ? 8 : 4;
   MMNAS_REQUIRE((size_t)k.B * nsl * 16 * 256 <= wsf && k.B <= ncnt, MMNAS_E_SHAPE, "ffn_small_fwd: M=%d exceeds the hand-off workspace", op->M);
   const double M = op->M;
   ProfScope ps(MMNAS_K_SMALL, 2.0 * M * 256.0 * 1024.0 * 2.0, 4.0 * (2.0 * 256.0 * 1024.0 + M * (3.0 * 256.0 + 1024.0)), st, "ffn_small_fwd");
@@ -1008,20 +993,6 @@ int ffn_small_fwd(const mmnas_mlp_op* op, float* h, float* z, hipStream_t st) {
 
 }  // namespace mmnas
 
-extern "C" int mmnas_set_small_ffn(int on) {
-  const int prev = mmnas::small_ffn_on() ? 1 : 0;
-  mmnas::g_small_ffn = on < 0 ? 0 : (on > 2 ? 2 : on);
-  return prev;
-}
-
-extern "C" int mmnas_set_small_bwd(int on) {
-  const int prev = mmnas::small_bwd_on() ? 1 : 0;
-  mmnas::g_small_bwd = on ? 1 : 0;
-  return prev;
-}
-
-extern "C" int mmnas_set_small_ops(int on) {
-  const int prev = mmnas::small_ops_on() ? 1 : 0;
-  mmnas::g_small_ops = on ? 1 : 0;
-  return prev;
-}
+extern "C" int mmnas_set_small_ffn(int on) { return mmnas::sw::small_ffn.set(on < 0 ? 0 : (on > 2 ? 2 : on)); }
+extern "C" int mmnas_set_small_bwd(int on) { return mmnas::sw::small_bwd.set(on != 0); }
+extern "C" int mmnas_set_small_ops(int on) { return mmnas::sw::small_ops.set(on != 0); }

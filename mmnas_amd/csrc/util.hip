@@ -1,12 +1,14 @@
-// Error plumbing, ABI version, and the small utility kernels of the C ABI:
+// Error plumbing, ABI version, the runtime switches (switches.h), and the small utility kernels of the C ABI:
 // dropout-mask materialisation (tests / mask replay), segment pack/unpack for the data-parallel
 // gradient exchange, fused Adam / SGD and sum-of-squares for the optimizer step.
 #include <stdarg.h>
+#include <stdlib.h>
 #include <string.h>
 #include <mutex>
 #include <vector>
 #include <algorithm>
 #include "common.h"
+#include "switches.h"
 
 namespace mmnas {
 
@@ -26,6 +28,62 @@ int check_launch(const char* what) {
     return MMNAS_E_LAUNCH;
   }
   return MMNAS_OK;
+}
+
+// ---- runtime switches: the definitions of switches.h's table ----
+int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e && e[0] ? atoi(e) : dflt;
+}
+
+namespace sw {
+#define MMNAS_SW_DEFINE(id, var, dflt, kind, policy, help) Switch id = {var, dflt, sw_##kind, sw_##policy, "[" #kind ", " #policy "] " help, 0, 0};
+MMNAS_SWITCHES(MMNAS_SW_DEFINE)
+#undef MMNAS_SW_DEFINE
+}  // namespace sw
+
+#define MMNAS_SW_ADDRESS(id, var, dflt, kind, policy, help) &sw::id,
+static Switch* const g_switches[] = {MMNAS_SWITCHES(MMNAS_SW_ADDRESS)};
+#undef MMNAS_SW_ADDRESS
+constexpr int N_SWITCHES = (int)(sizeof(g_switches) / sizeof(g_switches[0]));
+
+// what the environment says now; *from_env: the variable, not the default, decided
+static int sw_parse(const Switch& s, bool* from_env) {
+  const char* e = getenv(s.name);
+  *from_env = s.kind == sw_presence ? e != nullptr : (e && e[0]);
+  switch (s.kind) {
+    case sw_presence: case sw_string: return *from_env ? 1 : 0;
+    case sw_exact1: return e && e[0] == '1';
+    case sw_bool: return (*from_env ? atoi(e) : s.dflt) != 0;
+    default: return *from_env ? atoi(e) : s.dflt;
+  }
+}
+
+int Switch::read() {
+  bool from_env;
+  const int v = sw_parse(*this, &from_env);
+  if (policy != sw_every_call) { value = v; state = from_env ? 2 : 1; }
+  return v;
+}
+
+int Switch::reload() {
+  state = 0;
+  return read();
+}
+
+int Switch::set(int v) {
+  const int prev = get();
+  value = v;
+  state = 3;
+  return prev;
+}
+
+int Switch::peek(int* source) const {
+  if (state) { *source = state - 1; return value; }
+  bool from_env;
+  const int v = sw_parse(*this, &from_env);
+  *source = (from_env ? MMNAS_SWITCH_ENV : MMNAS_SWITCH_DEFAULT) | (policy == sw_every_call ? 0 : MMNAS_SWITCH_UNREAD);
+  return v;
 }
 
 // ---- optional per-kernel-class timing with HIP events on the launch stream (bench.py roofline) ----
@@ -285,7 +343,7 @@ extern "C" int mmnas_prof_collect(mmnas_prof_stat* stats) {
   std::lock_guard<std::mutex> g(prof::mu);
   for (int k = 0; k < MMNAS_K_COUNT; ++k) { stats[k].ms = 0; stats[k].flops = 0; stats[k].bytes = 0; stats[k].launches = 0; }
   // tuning aid: MMNAS_PROF_DUMP=<file> appends one "kind,tag,ms,flops,bytes" row per bracketed launch
-  const char* dump = getenv("MMNAS_PROF_DUMP");
+  const char* dump = getenv(sw::prof_dump.name);
   FILE* df = dump && dump[0] ? fopen(dump, "a") : nullptr;
   for (const prof::Rec& r : prof::recs) {
     if (r.kind < 0) continue;
@@ -303,6 +361,21 @@ extern "C" int mmnas_prof_collect(mmnas_prof_stat* stats) {
 }
 
 extern "C" int mmnas_abi_version(void) { return MMNAS_ABI_VERSION; }
+
+extern "C" int mmnas_switch_count(void) { return N_SWITCHES; }
+
+extern "C" int mmnas_switch_info(int i, const char** name, const char** help, int* dflt, int* value, int* source) {
+  MMNAS_REQUIRE(i >= 0 && i < N_SWITCHES, MMNAS_E_ARG, "mmnas_switch_info: index %d outside 0..%d", i, N_SWITCHES - 1);
+  const Switch& s = *g_switches[i];
+  int src = 0;
+  const int v = s.peek(&src);
+  if (name) *name = s.name;
+  if (help) *help = s.help;
+  if (dflt) *dflt = s.dflt;
+  if (value) *value = v;
+  if (source) *source = src;
+  return MMNAS_OK;
+}
 extern "C" const char* mmnas_last_error(void) { return g_err; }
 
 extern "C" int mmnas_dropout_mask(float* out, size_t n, float p, uint64_t seed, uint32_t site, void* stream) {

@@ -19,10 +19,11 @@ What is different from DDP, and why:
 Gradients are AVERAGED over ranks, as DDP does; the loss keeps reduction='sum' per rank.
 """
 import ctypes as C
-import os
 
 import torch
 import torch.distributed as dist
+
+from . import switches
 
 
 def _world():
@@ -187,7 +188,7 @@ def _chain_marks(red, op_params, bucket_of, buckets):
 
 
 # MMNAS_DP_TAIL_MAIN=0 restores round 5's end of step (everything on the communication stream, one scatter per bucket)
-_TAIL_ON_MAIN = os.environ.get('MMNAS_DP_TAIL_MAIN', '1') != '0'
+_TAIL_ON_MAIN = switches.DP_TAIL_MAIN.get()
 
 
 def _row_sparse_index(fg, comm, is_cuda):
@@ -196,7 +197,7 @@ def _row_sparse_index(fg, comm, is_cuda):
     completes LAST in backward (nothing is left to overlap a dense all-reduce with) and is half of everything the
     d = 256 supernet exchanges per step.  Only the first parameter of the flat buffer is taken (a bucket then simply
     starts behind it)."""
-    if not (comm and is_cuda and fg.params) or os.environ.get('MMNAS_DP_ROWS', '1') == '0':   # (0: dense, for A/B runs)
+    if not (comm and is_cuda and fg.params) or not switches.DP_ROWS.get():   # (0: dense, for A/B runs)
         return None
     return 0 if getattr(fg.params[0], '_mmnas_row_sparse', False) else None
 
@@ -307,7 +308,7 @@ def _inline_collectives(group, is_cuda):
     communication stream, no event pair per bucket (each cross-stream hop is ~10 us of idle queue at the end of a step,
     where nothing is left to overlap it).  The host does not block (a wait on a CUDA work object only orders streams).
     MMNAS_DP_INLINE=0 restores async_op=True + work.wait()."""
-    if not is_cuda or os.environ.get('MMNAS_DP_INLINE', '1') == '0':
+    if not is_cuda or not switches.DP_INLINE.get():
         return False
     try:
         return dist.get_backend(group) == 'nccl'
@@ -687,7 +688,7 @@ class SupernetReducer:
                     w = 'inline'
                 else:
                     w = dist.all_reduce(stg, op=op, group=self.group, async_op=True)
-                if avg and not self.inline and os.environ.get('MMNAS_DP_EARLY_SCATTER', '0') == '1':
+                if avg and not self.inline and switches.DP_EARLY_SCATTER.get():
                     # Optional (MMNAS_DP_EARLY_SCATTER=1): scatter the averaged gradients back as soon as THIS bucket's
                     # all-reduce ends (RCCL: wait() only makes the communication stream wait), leaving only the last
                     # bucket's scatter behind the end of backward.  Measured in a one-rank group: +0.06 ms per step --

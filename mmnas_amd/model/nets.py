@@ -8,20 +8,19 @@ Stem and head: embedding + LSTM stay on torch (MIOpen); every Linear (imgfeat_li
 embeddings, AttFlat, the projections) and every LayerNorm run on the HIP GEMM / LayerNorm kernels.
 """
 import ctypes
-import os
 
 import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import ops, zeroterm
+from .. import ops, switches, zeroterm
 from ..utils.ops_adapter import OpsAdapter
 from .mixed import MixedOp, sample_indices, sample_rows
 from .modules import AttFlat, LayerNorm, RelHandle
 
 OPS_ADAPTER = OpsAdapter()
-LAZY_REL = os.environ.get('MMNAS_LAZY_REL', '1') != '0'   # 0: materialise rel embeddings as the reference does
+LAZY_REL = switches.LAZY_REL.get()   # 0: materialise rel embeddings as the reference does
 
 # MCAN-style prior the supernet's alphas start from (hygr_vqa.py:138-156)
 _PRIOR = {'enc': ['self_att_64', 'feed_forward'] * 6,

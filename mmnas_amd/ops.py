@@ -11,6 +11,7 @@ import threading
 import torch
 
 from . import _lib as L
+from . import switches as S
 
 # ------------------------------------------------------------------------------------------
 # dropout seeds: every operator call in training mode draws a fresh 64-bit seed; kernels derive
@@ -43,7 +44,9 @@ _sinks_on = [True]
 def runtime_config():
     """What this process runs the library with: where the shared object came from, the launch configuration the library
     established at import (`_lib._launch_configuration`: HIP_FORCE_DEV_KERNARG and who set it) and every MMNAS_* / HIP_* /
-    NCCL_* / RCCL_* switch of the environment.  bench.py records it; an integrator prints it once."""
+    NCCL_* / RCCL_* switch of the environment, and under 'switches' what every MMNAS_* switch of the two tables is running with
+    (value, default and whether the value comes from the default, the environment or a set call).  bench.py records it; an
+    integrator prints it once."""
     return {
         'lib_path': L.LIB_PATH,
         'lib_loaded': L._lib is not None,
@@ -53,6 +56,7 @@ def runtime_config():
         'hip_initialised': torch.cuda.is_initialized(),
         'torch': torch.__version__, 'hip': getattr(torch.version, 'hip', None),
         'env': {k: v for k, v in sorted(os.environ.items()) if k.startswith(('MMNAS_', 'HIP_', 'NCCL_', 'RCCL_', 'HSA_'))},
+        'switches': S.report() if os.path.exists(L.LIB_PATH) else None,
     }
 
 
@@ -441,7 +445,7 @@ def gemm_pair(dgrad, wgrad):
 
 def _glimpse1_on():
     """MMNAS_HEAD_GLIMPSE1=0: the one-unit linear layers as GEMM launches (A/B, tests) -- read per call, like the native head."""
-    return os.environ.get('MMNAS_HEAD_GLIMPSE1', '1') != '0'
+    return S.HEAD_GLIMPSE1.get()
 
 
 class LinearFn(torch.autograd.Function):
@@ -599,8 +603,7 @@ def lstm(x, mod):
 
 def lstm_enabled():
     """The persistent-kernel LSTM is the default; MMNAS_LSTM=0 falls back to nn.LSTM (MIOpen: ~110 launches per step)."""
-    import os
-    return os.environ.get('MMNAS_LSTM', '1') != '0'
+    return S.LSTM.get()
 
 
 def lstm_supported(x, mod):
@@ -653,20 +656,13 @@ def layer_norm(x, a, b, eps=1e-6):
 # is written forward; the backward recomputes the normalised row from the saved attfc_y output and two statistics per row.
 # Opt-in: MMNAS_VGD_HEAD=1 (or set_vgd_head(True)) makes the VGD branch of the nets call it.  Off by default.
 # ------------------------------------------------------------------------------------------
-_vgd_head = [None]
-
-
 def vgd_head_enabled():
-    if _vgd_head[0] is None:
-        _vgd_head[0] = os.environ.get('MMNAS_VGD_HEAD', '0') == '1'
-    return _vgd_head[0]
+    return S.VGD_HEAD.get()
 
 
 def set_vgd_head(on):
     """Switch the fused grounding head of the VGD nets on / off (returns the previous setting)."""
-    prev = vgd_head_enabled()
-    _vgd_head[0] = bool(on)
-    return prev
+    return S.VGD_HEAD.set(bool(on))
 
 
 def _f32c16(t):
@@ -966,9 +962,10 @@ def conv_seq(x, weight, bias):
     # (overlapping rows read past an operand's M * lda extent: only the buffer-load path answers that with zeros)
     # (and the padded grid computes S + 2 pad rows per sequence: for the 14-token stream with wide kernels the window
     #  buffer is the cheaper form -- profiles/r04_conv_microbench.txt)
-    direct = (x.is_cuda and ci % 32 == 0 and co % 32 == 0 and os.environ.get('MMNAS_CONV_IM2COL', '0') != '1'
-              and (x.shape[1] + 2 * (k // 2) <= 1.25 * x.shape[1] or os.environ.get('MMNAS_CONV_IM2COL') == '0')
-              and os.environ.get('MMNAS_GEMM_GENERIC') is None and 4.0 * x.shape[0] * (x.shape[1] + k) * max(ci, co) * k < 3.9e9)
+    im2col = S.CONV_IM2COL.get()   # 1: always the window buffer; 0: direct whenever the shape allows; None: the row-count rule below
+    direct = (x.is_cuda and ci % 32 == 0 and co % 32 == 0 and im2col != 1
+              and (x.shape[1] + 2 * (k // 2) <= 1.25 * x.shape[1] or im2col == 0)
+              and not S.GEMM_GENERIC.get() and 4.0 * x.shape[0] * (x.shape[1] + k) * max(ci, co) * k < 3.9e9)
     if not direct:
         return _conv_seq_im2col(x, weight, bias)
     return ConvSeqFn.apply(x, weight, bias)
@@ -1045,16 +1042,14 @@ def attflat_pool(logits, x, mask):
 # backbone chain: all cell operators of a backbone in one C call per direction
 # ------------------------------------------------------------------------------------------
 def chain_enabled():
-    import os
-    return os.environ.get('MMNAS_CHAIN', '1') != '0'
+    return S.CHAIN.get()
 
 
 def mixed_chain_enabled():
     """Architecture step (MixedOp modes 'full' / 'two') through the backbone chain: every evaluated candidate in one native
     call per direction, the candidates' LayerNorms and the gated sum of a node as one kernel.  MMNAS_MIXED_CHAIN=0 keeps
     the per-candidate path (one autograd node per candidate + ops.MixedSumFn)."""
-    import os
-    return os.environ.get('MMNAS_MIXED_CHAIN', '1') != '0'
+    return S.MIXED_CHAIN.get()
 
 
 def side_stream_enabled():
@@ -1062,9 +1057,7 @@ def side_stream_enabled():
     the supernet and training steps it does not pay -- unpaired data- / weight-gradient launches cost more than the
     paired ones save, and workgroups of the deferred products delay the short, latency-bound encoder / LSTM kernels they
     were meant to fill the gaps of (6.99 -> 7.05 ms released per operator, 7.35 ms released per phase)."""
-    import os
-    v = os.environ.get('MMNAS_SIDE_STREAM', '0')
-    return 2 if v == 'rel' else int(v == '1')   # 'rel': only the relation-bias backward (parameter gradients only) moves
+    return S.SIDE_STREAM.get()   # 0 / 1 / 2 ('rel': only the relation-bias backward (parameter gradients only) moves)
 
 
 _side_pending = []          # arenas / inputs the side stream may still be reading (released by join_side_stream)
@@ -1147,7 +1140,7 @@ def _grad_ptr(p):
 # AccumulateGrad nodes, 230 zero + gradient adds -- and stock clip_grad_norm_ + Adam over 900 tensors are 6.3 ms).  Kept,
 # tested against the per-operator nodes and the reference, for callers whose loop is not host-bound.
 def autograd_chain_enabled():
-    return os.environ.get('MMNAS_AUTOGRAD_CHAIN', '0') == '1'
+    return S.AUTOGRAD_CHAIN.get()
 
 
 def _null_ptr(_p):
@@ -1305,20 +1298,13 @@ def _release_sinks(ctx, params):
 # decoder OUTPUT rows of the padding are zeros instead of the reference's (unread) values, and dropout draws from other
 # element indices.  Off by default.
 # ------------------------------------------------------------------------------------------
-_unpad = [None]
-
-
 def unpad_enabled():
-    if _unpad[0] is None:
-        _unpad[0] = os.environ.get('MMNAS_UNPAD', '0') == '1'
-    return _unpad[0]
+    return S.UNPAD.get()
 
 
 def set_unpad(on):
     """Switch the ragged decoder stream on / off (returns the previous setting)."""
-    prev = unpad_enabled()
-    _unpad[0] = bool(on)
-    return prev
+    return S.UNPAD.set(bool(on))
 
 
 class Ragged:

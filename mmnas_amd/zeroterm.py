@@ -26,14 +26,14 @@ turns the loss into NaN through `0 * inf` (the loss itself still does), and the 
 when the incoming gradient of the loss is non-finite.  `MMNAS_ZERO_TERMS=0` keeps plain parameters (the literal lines
 then run as written).
 """
-import os
-
 import torch
 from torch import nn
 
+from . import switches
+
 
 def enabled():
-    return os.environ.get('MMNAS_ZERO_TERMS', '1') != '0'
+    return switches.ZERO_TERMS.get()
 
 
 class _ZeroGrads(torch.autograd.Function):
