@@ -1410,7 +1410,8 @@ extern "C" int mmnas_chain_bwd(const mmnas_chain* c, void* stream) {
   // When the queued parameter-gradient work is released: MMNAS_SIDE_FLUSH=op -> behind every operator (it then competes
   // with the data-gradient chain for the CUs); default -> once behind the decoder and once behind the encoder, so it
   // fills the latency-bound tail of the backward pass (encoder on 896 rows, LSTM, stem) instead.
-  static const bool per_op = getenv(sw::side_flush.name) && !strcmp(getenv(sw::side_flush.name), "op");
+  // (get(): the row records that it was read, so mmnas_switch_info reports it as it reports every cached switch)
+  static const bool per_op = sw::side_flush.get() && !strcmp(getenv(sw::side_flush.name), "op");
   char* base = (char*)c->arena;
   const size_t ex = (size_t)c->B * c->Sx * c->d, ey = chain_rows_y(c) * c->d;
   float* dpre = (float*)(base + L.dpre);

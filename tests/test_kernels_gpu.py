@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests.kernel_refs import mha_ref as _mha_ref, rel_fused_ref, rel_multi_pre, rel_multi_ref
 from tests.util import TOL, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -98,6 +99,17 @@ def test_gemm_layouts(layout, M, N, K, tile, mode, gemm_tuning):
     ops.gemm(lay, [dict(M=M, A=[Ad], B=[Bd], C=Cd)], N, K, lda, ldb, N, split_k=split)
     err = rel_err(Cd.cpu().numpy(), ref.numpy())
     assert err < 1e-5, err
+
+
+@pytest.mark.parametrize('layout', ['NT', 'NN', 'TN'])
+@pytest.mark.parametrize('M,N,K', [(300, 192, 160), (257, 130, 100), (896, 512, 512)])
+@pytest.mark.parametrize('mode', [6, 0])
+@pytest.mark.parametrize('knob', [dict(pf=1), dict(xcd=0), dict(generic=1)], ids=['pf1', 'xcd0', 'generic'])
+def test_gemm_reload_policy_switches(layout, M, N, K, mode, knob, gemm_tuning):
+    """MMNAS_GEMM_PF=1 (one K-tile of operand loads in flight in the 64^2 fp32 kernels), MMNAS_GEMM_XCD=0 (identity workgroup
+    mapping) and MMNAS_GEMM_GENERIC (set: the guarded-load path whatever the shape; unset again when the fixture restores the
+    environment): same products, test_gemm_layouts' bound."""
+    test_gemm_layouts(layout, M, N, K, 0, mode, lambda **kw: gemm_tuning(**dict(kw, **knob)))
 
 
 @pytest.mark.parametrize('layout', ['NT', 'NN', 'TN'])
@@ -588,13 +600,8 @@ def test_rel_fused_lazy_handle(B, Sq, Sk, C, H):
     biasT = torch.empty(B, H, Sk, Sq, device=DEV)
     L.check(L.lib().mmnas_rel_fused_fwd(L.fptr(rawd), L.fptr(Wyd), L.fptr(byd), L.fptr(Wrd), L.fptr(brd), L.fptr(biasT),
                                         B, Sq, Sk, C, R, H, L.stream()))
-    T = lambda a: torch.from_numpy(a).double().requires_grad_(True)
-    Wyt, byt, Wrt, brt = T(Wy), T(by), T(Wr), T(br)
-    rel = torch.relu(torch.from_numpy(raw).double() @ Wyt.t() + byt)
-    r = torch.relu(rel @ Wrt.t() + brt)
-    bias = torch.log(torch.clamp(r, min=1e-6)).permute(0, 3, 2, 1)
-    assert rel_err(biasT.cpu().numpy(), bias.detach().numpy()) < TOL
-    bias.backward(torch.from_numpy(gb).double())
+    bias, rdWy, rdby, rdWr, rdbr = rel_fused_ref(raw, Wy, by, Wr, br, gb)
+    assert rel_err(biasT.cpu().numpy(), bias) < TOL
     dWy, dby = torch.zeros(R, C, device=DEV), torch.zeros(R, device=DEV)
     dWr, dbr = torch.zeros(H, R, device=DEV), torch.zeros(H, device=DEV)
     ws = torch.empty(L.lib().mmnas_rel_fused_bwd_ws_floats(B, Sq, Sk), device=DEV)
@@ -604,10 +611,10 @@ def test_rel_fused_lazy_handle(B, Sq, Sk, C, H):
     # 1/r-amplified random-sign sums over 20000 elements (see test_rel_bias); here they are additionally
     # accumulated as one sequential fp32 fma chain per workgroup on the MFMA
     wtol = 6e-3 if B * Sq * Sk > 5000 else TOL
-    assert rel_err(dWr.cpu().numpy(), Wrt.grad.numpy()) < wtol
-    assert rel_err(dbr.cpu().numpy(), brt.grad.numpy()) < wtol
-    assert rel_err(dWy.cpu().numpy(), Wyt.grad.numpy()) < wtol
-    assert rel_err(dby.cpu().numpy(), byt.grad.numpy()) < wtol
+    assert rel_err(dWr.cpu().numpy(), rdWr) < wtol
+    assert rel_err(dbr.cpu().numpy(), rdbr) < wtol
+    assert rel_err(dWy.cpu().numpy(), rdWy) < wtol
+    assert rel_err(dby.cpu().numpy(), rdby) < wtol
 
 
 @pytest.mark.parametrize('B,S,C,H,lens', [(4, 100, 4, 4, [100, 37, 10, 1]), (3, 100, 4, 8, [64, 100, 33]), (5, 14, 3, 4, [14, 3, 7, 1, 9]),
@@ -697,10 +704,8 @@ def test_rel_multi_all_relation_operators_in_one_launch(B, S, C, H, n_ops, lens)
     # side of it depending on the last bit, and weighs up to 1e6 in the sums.  The test keeps such elements out of the
     # gradient (zero bias gradient inside the band |pre| < 0.05) so that what is left is well-conditioned and can be held to
     # a tight bound; elements safely BELOW the clamp keep a non-zero bias gradient (their contribution must be exactly zero).
-    rel64 = torch.relu(torch.from_numpy(raw).double() @ torch.from_numpy(Wy).double().t() + torch.from_numpy(by).double())
     for i in range(n_ops):
-        pre = (rel64 @ torch.from_numpy(Wrs[i]).double().t() + torch.from_numpy(brs[i]).double()).permute(0, 3, 2, 1).numpy()
-        gbs[i] = np.where(np.abs(pre) < 0.05, 0.0, gbs[i]).astype(np.float32)
+        gbs[i] = np.where(np.abs(rel_multi_pre(raw, Wy, by, Wrs[i], brs[i])) < 0.05, 0.0, gbs[i]).astype(np.float32)
     # outside the valid corners the bias gradient is never read: poison it
     gbd = [g(np.where(valid > 0, gb, np.nan).astype(np.float32)) for gb in gbs]
     bias = [torch.full((B, H, S, S), 12345.0, device=DEV) for _ in range(n_ops)]
@@ -719,16 +724,9 @@ def test_rel_multi_all_relation_operators_in_one_launch(B, S, C, H, n_ops, lens)
     L.check(lib.mmnas_rel_multi_bwd(C_.byref(m), L.stream()))
     torch.cuda.synchronize()
     # float64 restatement
-    T = lambda a: torch.from_numpy(a).double().requires_grad_(True)
-    Wyt, byt = T(Wy), T(by)
-    rel = torch.relu(torch.from_numpy(raw).double() @ Wyt.t() + byt)
+    r_ref, rdWr, rdbr, rdWy, rdby = rel_multi_ref(raw, Wy, by, Wrs, brs, gbs, valid)
     vm = torch.from_numpy(valid).double()
-    refs = []
-    for i in range(n_ops):
-        Wrt, brt = T(Wrs[i]), T(brs[i])
-        r = torch.clamp(torch.relu(rel @ Wrt.t() + brt), min=1e-6).permute(0, 3, 2, 1)      # [B, H, S_k, S_q]
-        (torch.log(r) * torch.from_numpy(gbs[i]).double() * vm).sum().backward(retain_graph=True)
-        refs.append((r.detach(), Wrt.grad, brt.grad))
+    refs = [(torch.from_numpy(r_ref[i]), torch.from_numpy(rdWr[i]), torch.from_numpy(rdbr[i])) for i in range(n_ops)]
     wtol = 1e-4
     for i in range(n_ops):
         got = bias[i].cpu()
@@ -738,8 +736,8 @@ def test_rel_multi_all_relation_operators_in_one_launch(B, S, C, H, n_ops, lens)
         assert float(((rr - refs[i][0]).abs() * vm).max()) <= 2e-5 * scale, i
         assert rel_err(dWr[i].cpu().numpy(), refs[i][1].numpy()) < wtol, i
         assert rel_err(dbr[i].cpu().numpy(), refs[i][2].numpy()) < wtol, i
-    assert rel_err(dWy.cpu().numpy(), Wyt.grad.numpy()) < wtol
-    assert rel_err(dby.cpu().numpy(), byt.grad.numpy()) < wtol
+    assert rel_err(dWy.cpu().numpy(), rdWy) < wtol
+    assert rel_err(dby.cpu().numpy(), rdby) < wtol
     # ... and the per-operator kernels: same numbers to round-off (another summation order over the same terms)
     p_dWy, p_dby = torch.zeros(R, C, device=DEV), torch.zeros(R, device=DEV)
     ws1 = torch.empty(lib.mmnas_rel_fused_bwd_ws_floats(B, S, S), device=DEV)
@@ -850,23 +848,6 @@ def test_attflat_pool(B, S, d, G, use_mask):
 
 
 # ----------------------------------------------------------------------------- attention core
-def _mha_ref(Q, K, V, mask, biasT, H, dh, dmask=None):
-    B, Sq, _ = Q.shape
-    Sk = K.shape[1]
-    q = Q.reshape(B, Sq, H, dh).permute(0, 2, 1, 3)
-    k = K.reshape(B, Sk, H, dh).permute(0, 2, 1, 3)
-    v = V.reshape(B, Sk, H, dh).permute(0, 2, 1, 3)
-    z = q @ k.transpose(-1, -2) / math.sqrt(dh)
-    if biasT is not None:
-        z = z + biasT.permute(0, 1, 3, 2)
-    if mask is not None:
-        z = z.masked_fill(mask.reshape(B, 1, 1, Sk), -1e9)
-    a = torch.softmax(z, -1)
-    if dmask is not None:
-        a = a * dmask
-    return (a @ v).permute(0, 2, 1, 3).reshape(B, Sq, H * dh)
-
-
 @pytest.mark.parametrize('B,H,Sq,Sk,dh,use_mask,use_bias,p', [
     (2, 2, 7, 7, 64, True, False, 0.0), (2, 8, 100, 100, 64, True, True, 0.0), (2, 8, 100, 14, 64, True, False, 0.1),
     (3, 4, 14, 14, 64, True, False, 0.0), (2, 2, 36, 50, 64, True, False, 0.0), (2, 4, 9, 9, 32, True, True, 0.0),
@@ -922,6 +903,20 @@ def test_mha_core(B, H, Sq, Sk, dh, use_mask, use_bias, p):
     assert rel_err(dV.cpu().numpy(), Vt.grad.numpy()) < 1e-4
     if use_bias:
         assert rel_err(dbT.cpu().numpy(), bt.grad.numpy()) < 1e-4
+
+
+@pytest.mark.parametrize('B,H,Sq,Sk,dh,use_mask,use_bias,p', [
+    (2, 8, 100, 14, 64, True, False, 0.1), (1, 2, 130, 130, 64, True, False, 0.0), (2, 4, 70, 33, 32, True, False, 0.0),
+    (1, 2, 150, 31, 128, True, False, 0.0), (2, 2, 50, 200, 64, True, True, 0.2)])
+def test_mha_core_two_wave_workgroups(B, H, Sq, Sk, dh, use_mask, use_bias, p, monkeypatch):
+    """MMNAS_MHA_NW=2 (read at every launch; launch_fwd / launch_bwd of attention.hip), at test_mha_core's shapes outside the bf16
+    cores' range and at its bounds.  What each row changes: (100, 14): the forward, mha_fwd_kernel<64,1,2> for <64,1,4> (its
+    backward is the fused kernel either way); (130, 130), (70, 33), (150, 31): the forward and mha_bwd_q_kernel on 2 waves,
+    and for 130 keys mha_bwd_kv_kernel<.,2,1> for <.,4,1>; (50, 200): only mha_bwd_kv_kernel<64,2,1> for <64,4,1> (50 queries
+    take 2-wave groups anyway).  Inside the bf16 range the switch matters only beside MMNAS_MHA_FWD_B16=0 /
+    MMNAS_MHA_BWD_FUSED=0, read once: tests/test_fallback_paths_gpu.py."""
+    monkeypatch.setenv('MMNAS_MHA_NW', '2')
+    test_mha_core(B, H, Sq, Sk, dh, use_mask, use_bias, p)
 
 
 @pytest.mark.parametrize('Sq,Sk,use_bias,p', [(100, 100, True, 0.1), (128, 128, False, 0.0), (36, 65, True, 0.0)])

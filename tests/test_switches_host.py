@@ -267,3 +267,129 @@ def test_both_parsers_agree_where_both_sides_read_a_variable():
                      '    out.append([t["MMNAS_HEAD_GLIMPSE1"][1], int(S.HEAD_GLIMPSE1.get()), t["MMNAS_GEMM_GENERIC"][1], int(S.GEMM_GENERIC.get())])\n'
                      'print(json.dumps(out))\n')
     assert _child(code) == [[1, 1, 0, 0], [0, 0, 1, 1], [1, 1, 1, 1]]
+
+
+# ---------------------------------------------------------------------------------------- 8. the fallback cases and the ledger
+def _native_rows():
+    """name -> [kind, default] of the native table ('[kind, policy] ...' opens every help text)."""
+    code = NATIVE + ('out = {}\n'
+                     'n, h, d, v, s = C.c_char_p(), C.c_char_p(), C.c_int(), C.c_int(), C.c_int()\n'
+                     'for i in range(lib.mmnas_switch_count()):\n'
+                     '    assert lib.mmnas_switch_info(i, C.byref(n), C.byref(h), C.byref(d), C.byref(v), C.byref(s)) == 0\n'
+                     '    out[n.value.decode()] = [h.value.decode()[1:].split(",")[0], d.value]\n'
+                     'print(json.dumps(out))\n')
+    return _child(code)
+
+
+def _parsed(kind, text):
+    """What the native parser makes of a case's value (csrc/util.hip sw_parse), for the documented inputs the cases use."""
+    if kind in ('presence', 'string'):
+        return 1
+    if kind == 'exact1':
+        return int(text.startswith('1'))
+    return int(text != '0') if kind == 'bool' else int(text)
+
+
+def test_every_fallback_case_sets_native_rows_away_from_their_defaults():
+    from tests import fallback_cases as F
+    rows = _native_rows()
+    assert len(F.CASES) >= 11
+    for name, case in F.CASES.items():
+        assert case['env'] and case['shapes'] and case['kind'] in F.RUNNERS, name
+        assert F.REACHES.get(name), name      # every case says which kernels it is there for
+        for k, text in case['env'].items():
+            assert k in rows, (name, k)
+            kind, dflt = rows[k]
+            assert _parsed(kind, text) != dflt, (name, k, text, dflt)
+        for shape in case['shapes']:
+            assert F.bounds_of(name, shape)
+
+
+# switches whose alternative side an existing test sets: variable -> (test file, how that file spells it when not by the
+# variable's name or its mmnas_set_* setter: a keyword of test_kernels_gpu.py's gemm_tuning fixture)
+COVERED_ELSEWHERE = {
+    'MMNAS_CHAIN_OVERLAP': ('test_chain_gpu.py', None), 'MMNAS_HEAD_GLIMPSE1': ('test_chain_gpu.py', None),
+    'MMNAS_REL_HOIST': ('test_chain_gpu.py', None), 'MMNAS_REL_OVERLAP': ('test_chain_gpu.py', None),
+    'MMNAS_GUIDED_HOIST': ('test_chain_gpu.py', None), 'MMNAS_SMALL_OPS': ('test_small_gpu.py', None),
+    'MMNAS_SMALL_BWD': ('test_small_gpu.py', None), 'MMNAS_SMALL_FFN': ('test_small_gpu.py', None),
+    'MMNAS_GEMM_LN': ('test_gemm_ln_gpu.py', None),
+    'MMNAS_HEAD_PROJT': ('test_fallback_paths_gpu.py', None), 'MMNAS_REL_FWD_VALU': ('test_fallback_paths_gpu.py', None),
+    'MMNAS_GEMM_SPLIT': ('test_kernels_gpu.py', 'split=mode'), 'MMNAS_GEMM_TILE': ('test_kernels_gpu.py', 'tile=tile'),
+    'MMNAS_GEMM_SK': ('test_kernels_gpu.py', 'sk=2'), 'MMNAS_GEMM_PAIR': ('test_kernels_gpu.py', 'pair=pair'),
+    'MMNAS_GEMM_LEAN': ('test_kernels_gpu.py', None), 'MMNAS_GEMM_PF': ('test_kernels_gpu.py', 'pf=1'),
+    'MMNAS_GEMM_XCD': ('test_kernels_gpu.py', 'xcd=0'), 'MMNAS_GEMM_GENERIC': ('test_kernels_gpu.py', 'generic=1'),
+}
+# switches nothing runs the other side of, with the reason (debug-build-only or pure tuning knobs only)
+NOT_COVERED = {}
+KERNEL_SELECTING_INTS = ('MMNAS_MHA_NW', 'MMNAS_REL_MULTI_YIELD', 'MMNAS_SMALL_FFN', 'MMNAS_GEMM_SPLIT', 'MMNAS_GEMM_TILE', 'MMNAS_GEMM_SK',
+                         'MMNAS_GEMM_PF', 'MMNAS_GEMM_XCD', 'MMNAS_GEMM_PAIR', 'MMNAS_GEMM_LEAN')
+
+
+def test_ledger_every_kernel_selecting_switch_has_a_test_of_its_other_side():
+    """Every native switch of kind bool / exact1, and every int switch whose help names alternative kernels, is set by a case of
+    tests/fallback_cases.py, by the existing test COVERED_ELSEWHERE names (checked: that file spells it), or is listed in
+    NOT_COVERED with its reason.  A switch added without a test fails here."""
+    from tests import fallback_cases as F
+    rows = _native_rows()
+    assert set(KERNEL_SELECTING_INTS) <= set(rows)
+    need = {k for k, (kind, _) in rows.items() if kind in ('bool', 'exact1')} | set(KERNEL_SELECTING_INTS)
+    by_case = {k for c in F.CASES.values() for k in c['env']}
+    assert not (set(COVERED_ELSEWHERE) | set(NOT_COVERED)) - set(rows), 'a ledger entry that is no native switch'
+    assert not set(NOT_COVERED) & (by_case | set(COVERED_ELSEWHERE))
+    missing = need - by_case - set(COVERED_ELSEWHERE) - set(NOT_COVERED)
+    assert not missing, sorted(missing)
+    for k, (fname, spelled) in COVERED_ELSEWHERE.items():
+        src = open(os.path.join(REPO, 'tests', fname)).read()
+        setter = 'mmnas_set_' + k[len('MMNAS_'):].lower()
+        if spelled is not None:
+            assert k.startswith('MMNAS_GEMM_') and spelled.split('=')[0] == k[len('MMNAS_GEMM_'):].lower(), k
+            assert 'def gemm_tuning' in src and re.search(r'gemm_tuning\([^)]*\b' + re.escape(spelled), src) or \
+                re.search(r'dict\(' + re.escape(spelled) + r'\)', src), (k, fname)
+        else:
+            assert "'%s'" % k in src or setter in src, (k, fname)
+    for k, why in NOT_COVERED.items():
+        assert isinstance(why, str) and why.strip(), k
+
+
+def test_fallback_runner_lists_its_cases_without_a_gpu():
+    from tests import fallback_cases as F
+    e = {k: v for k, v in os.environ.items() if not k.startswith('MMNAS_')}
+    e['CUDA_VISIBLE_DEVICES'] = e['HIP_VISIBLE_DEVICES'] = ''
+    p = subprocess.run([sys.executable, os.path.join(REPO, 'tests', 'fallback_cases.py'), '--list'], cwd=REPO, env=e,
+                       capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stderr[-3000:]
+    listed = [json.loads(l) for l in p.stdout.splitlines()]
+    assert [r['case'] for r in listed] == list(F.CASES)
+    for r in listed:
+        c = F.CASES[r['case']]
+        assert r['env'] == c['env'] and r['kind'] == c['kind'] and r['shapes'] == json.loads(json.dumps(c['shapes']))
+    p = subprocess.run([sys.executable, os.path.join(REPO, 'tests', 'fallback_cases.py'), 'no_such_case'], cwd=REPO, env=e,
+                       capture_output=True, text=True, timeout=120)
+    assert p.returncode == 2 and 'usage' in p.stderr and not p.stdout
+
+
+def test_fallback_references_against_torch():
+    """The float64 references the runner judges the kernels by (tests/kernel_refs.py), on the CPU: the attention core against
+    torch's scaled_dot_product_attention, and the relation bias's analytic gradients against a central difference."""
+    import numpy as np
+    import torch
+    from tests.kernel_refs import mha_ref, rel_fused_ref
+    rs = np.random.RandomState(5)
+    B, H, Sq, Sk, dh = 2, 3, 5, 7, 8
+    Q, K, V = (torch.from_numpy(rs.standard_normal((B, s, H * dh))) for s in (Sq, Sk, Sk))
+    biasT = torch.from_numpy(rs.standard_normal((B, H, Sk, Sq)))
+    mask = torch.zeros(B, Sk, dtype=torch.bool)
+    mask[1, 4:] = True
+    split = lambda t: t.reshape(B, -1, H, dh).permute(0, 2, 1, 3)
+    am = biasT.permute(0, 1, 3, 2).masked_fill(mask.reshape(B, 1, 1, Sk), float('-inf'))
+    want = torch.nn.functional.scaled_dot_product_attention(split(Q), split(K), split(V), attn_mask=am).permute(0, 2, 1, 3).reshape(B, Sq, H * dh)
+    assert float((mha_ref(Q, K, V, mask, biasT, H, dh) - want).abs().max()) < 1e-12
+    raw = rs.standard_normal((2, 3, 4, 4))
+    Wy, by, Wr, br = rs.standard_normal((64, 4)) / 2, 0.1 * rs.standard_normal(64), rs.standard_normal((2, 64)) / 8, 0.1 * rs.standard_normal(2) + 1.0
+    gb = rs.standard_normal((2, 2, 4, 3))
+    bias, dWy, dby, dWr, dbr = rel_fused_ref(raw, Wy, by, Wr, br, gb)
+    assert bias.shape == (2, 2, 4, 3)
+    f = lambda b: float((rel_fused_ref(raw, Wy, by, Wr, b, gb)[0] * gb).sum())
+    for h in range(2):
+        e = np.zeros(2); e[h] = 1e-6
+        assert abs((f(br + e) - f(br - e)) / 2e-6 - dbr[h]) < 1e-5 * max(1.0, abs(dbr[h]))
