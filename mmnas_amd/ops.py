@@ -105,6 +105,12 @@ def _bytes(n, dev):
     return torch.empty(max(int(n), 256), dtype=torch.uint8, device=dev)
 
 
+def _ws_floats(n, dev):
+    """Kernel scratch of `n` floats (a *_ws_floats() promise).  With _bytes the one place scratch and
+    arenas come from, so that the guard-band tests can hand out blocks of exactly the promised size."""
+    return torch.empty(int(n), dtype=torch.float32, device=dev)
+
+
 def _f32c(t):
     if t.dtype != torch.float32:
         raise L.MMNasHipError('mmnas_amd operators compute in float32; got %s' % t.dtype)
@@ -485,7 +491,7 @@ class LinearFn(torch.autograd.Function):
         (dW, db), rets, sinks = _grad_bufs(ctx.params, x.device)
         if ctx.one:
             dx = torch.empty_like(x)   # (always formed: the kernel is one pass over x either way)
-            ws = torch.empty(L.lib().mmnas_glimpse1_bwd_ws_floats(M, K), dtype=torch.float32, device=x.device)
+            ws = _ws_floats(L.lib().mmnas_glimpse1_bwd_ws_floats(M, K), x.device)
             L.check(L.lib().mmnas_glimpse1_bwd(L.fptr(dy), L.fptr(x), L.fptr(W), L.fptr(dx), L.fptr(dW),
                                                L.fptr(db if ctx.has_bias else None), L.fptr(ws), M, K, L.stream()))
             for sk in sinks:
@@ -638,7 +644,7 @@ class LayerNormFn(torch.autograd.Function):
         M = x.numel() // d
         dx = torch.empty_like(x)
         dab = torch.zeros(2, d, dtype=torch.float32, device=x.device)
-        ws = torch.empty(L.lib().mmnas_layernorm_bwd_ws_floats(M, d), dtype=torch.float32, device=x.device)
+        ws = _ws_floats(L.lib().mmnas_layernorm_bwd_ws_floats(M, d), x.device)
         L.check(L.lib().mmnas_layernorm_bwd(L.fptr(x), L.fptr(a), L.fptr(dy), L.fptr(dx), L.fptr(dab[0]),
                                             L.fptr(dab[1]), None, None, L.fptr(ws), 0.0, 0, 0, M, d, ctx.eps,
                                             L.stream()))
@@ -702,7 +708,7 @@ class GroundingHeadFn(torch.autograd.Function):
         dyf = torch.empty_like(yf)
         sizes = [B * F, F, F, F, 4 * F, 1, 4]
         dxp, da, db, dWs, dWr, dbs, dbr = torch.split(torch.empty(sum(sizes), dtype=torch.float32, device=dev), sizes)
-        ws = torch.empty(L.lib().mmnas_vgd_head_bwd_ws_floats(B, S, F), dtype=torch.float32, device=dev)
+        ws = _ws_floats(L.lib().mmnas_vgd_head_bwd_ws_floats(B, S, F), dev)
         L.check(L.lib().mmnas_vgd_head_bwd(L.fptr(dscores), L.fptr(dreg), L.fptr(yf), L.fptr(xp), L.fptr(ln_a), L.fptr(ln_b),
                                            L.fptr(Ws), L.fptr(Wr), L.fptr(scores), L.fptr(stats[0]), L.fptr(stats[1]), L.fptr(dyf),
                                            L.fptr(dxp), L.fptr(da), L.fptr(db), L.fptr(dWs), L.fptr(dbs), L.fptr(dWr), L.fptr(dbr),
@@ -1686,7 +1692,7 @@ class MixedSumFn(torch.autograd.Function):
             dgate = torch.zeros(ctx.n, dtype=torch.float32, device=dout.device)
             ret = dgate
         d_active = torch.empty_like(dout)
-        ws = torch.empty(lib.mmnas_mixed_sum_ws_floats(), dtype=torch.float32, device=dout.device)
+        ws = _ws_floats(lib.mmnas_mixed_sum_ws_floats(), dout.device)
         L.check(lib.mmnas_mixed_sum_bwd(arr, ctx.n, L.fptr(g), L.fptr(dout), L.fptr(d_active), ctx.active, L.fptr(dgate),
                                         L.fptr(ws), dout.numel(), L.stream()))
         ctx.keep = None

@@ -6,7 +6,9 @@ import numpy as np
 import pytest
 import torch
 
-from tests.kernel_refs import mha_ref as _mha_ref, rel_fused_ref, rel_multi_pre, rel_multi_ref
+from tests.gemm_knobs import gemm_knobs
+from tests.kernel_refs import (attflat_pool_ref, eltwise_ref, glu_ref, mha_ref as _mha_ref, rel_bias_ref, rel_fused_ref,
+                               rel_multi_pre, rel_multi_ref)
 from tests.util import TOL, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -43,27 +45,7 @@ def test_dropout_mask_matches_numpy_restatement():
 @pytest.fixture
 def gemm_tuning():
     """Set MMNAS_GEMM_* scheduling knobs for one test (the library caches them: reload after every change)."""
-    import os
-    import mmnas_amd._lib as L
-    saved = {}
-
-    def set_knobs(**kw):
-        for k, v in kw.items():
-            name = 'MMNAS_GEMM_' + k.upper()
-            saved.setdefault(name, os.environ.get(name))
-            if v is None:
-                os.environ.pop(name, None)
-            else:
-                os.environ[name] = str(v)
-        L.lib().mmnas_gemm_reload_tuning()
-
-    yield set_knobs
-    for name, v in saved.items():
-        if v is None:
-            os.environ.pop(name, None)
-        else:
-            os.environ[name] = v
-    L.lib().mmnas_gemm_reload_tuning()
+    yield from gemm_knobs()
 
 
 @pytest.mark.parametrize('layout', ['NT', 'NN', 'TN'])
@@ -520,17 +502,14 @@ def test_colsum_eltwise_glu_dropadd():
     xdev = g(x)
     L.check(L.lib().mmnas_colsum(L.fptr(xdev), L.fptr(out), 777, 300, 300, L.stream()))
     assert rel_err(out.cpu().numpy(), x.astype(np.float64).sum(0)) < 1e-5
-    xt = torch.from_numpy(x).double().requires_grad_(True)
     gy = rnd(rs, 777, 300)
-    refs = {0: xt * 0., 1: torch.relu(xt), 2: torch.nn.functional.leaky_relu(xt, 0.01), 3: O.gelu_tanh(xt)}
-    for kind, r in refs.items():
+    for kind in range(4):
         xd = g(x).requires_grad_(True)
         y = ops.eltwise(xd, kind)
         y.backward(g(gy))
-        xt.grad = None
-        r.backward(torch.from_numpy(gy).double())
-        assert rel_err(y.detach().cpu().numpy(), r.detach().numpy()) < 1e-5, kind
-        assert rel_err(xd.grad.cpu().numpy(), xt.grad.numpy()) < 1e-5, kind
+        r, rdx = eltwise_ref(kind, x, gy)
+        assert rel_err(y.detach().cpu().numpy(), r.numpy()) < 1e-5, kind
+        assert rel_err(xd.grad.cpu().numpy(), rdx.numpy()) < 1e-5, kind
     # GLU with relu + dropout
     h = rnd(rs, 60, 256)
     hd = g(h).requires_grad_(True)
@@ -538,12 +517,9 @@ def test_colsum_eltwise_glu_dropadd():
     y = ops.glu(hd, relu=True, drop_p=p, seed=seed, site=0)
     gy = rnd(rs, 60, 128)
     y.backward(g(gy))
-    ht = torch.from_numpy(h).double().requires_grad_(True)
-    a, b = ht.chunk(2, -1)
-    r = torch.relu(a * torch.sigmoid(b)) * torch.from_numpy(dropout_rng.scaled_mask(seed, 0, (60, 128), p)).double()
-    r.backward(torch.from_numpy(gy).double())
-    assert rel_err(y.detach().cpu().numpy(), r.detach().numpy()) < 1e-5
-    assert rel_err(hd.grad.cpu().numpy(), ht.grad.numpy()) < 1e-5
+    r, rdh = glu_ref(h, gy, relu=True, dmask=dropout_rng.scaled_mask(seed, 0, (60, 128), p))
+    assert rel_err(y.detach().cpu().numpy(), r.numpy()) < 1e-5
+    assert rel_err(hd.grad.cpu().numpy(), rdh.numpy()) < 1e-5
     # drop_add
     xx, rr = rnd(rs, 40, 64), rnd(rs, 40, 64)
     z = ops.drop_add(g(xx), g(rr), 0.5, 77, 1)
@@ -563,24 +539,19 @@ def test_rel_bias(B, Sq, Sk, R, H):
     reld, Wd, bd = g(rel), g(Wr), g(br)
     biasT = torch.empty(B, H, Sk, Sq, device=DEV)
     L.check(L.lib().mmnas_rel_bias_fwd(L.fptr(reld), L.fptr(Wd), L.fptr(bd), L.fptr(biasT), B, Sq, Sk, R, H, L.stream()))
-    relt = torch.from_numpy(rel).double().requires_grad_(True)
-    Wt = torch.from_numpy(Wr).double().requires_grad_(True)
-    bt = torch.from_numpy(br).double().requires_grad_(True)
-    r = torch.relu(relt @ Wt.t() + bt)                      # [B,Sq,Sk,H]
-    bias = torch.log(torch.clamp(r, min=1e-6)).permute(0, 3, 2, 1)  # -> [B,H,Sk,Sq]
-    assert rel_err(biasT.cpu().numpy(), bias.detach().numpy()) < TOL
-    bias.backward(torch.from_numpy(gb).double())
+    bias, rdrel, rdW, rdb = rel_bias_ref(rel, Wr, br, gb)
+    assert rel_err(biasT.cpu().numpy(), bias.numpy()) < TOL
     drel = torch.empty_like(reld)
     dW, db = torch.zeros(H, R, device=DEV), torch.zeros(H, device=DEV)
     gbd = g(gb)
     L.check(L.lib().mmnas_rel_bias_bwd(L.fptr(reld), L.fptr(Wd), L.fptr(bd), L.fptr(gbd), L.fptr(drel), L.fptr(dW),
                                        L.fptr(db), 0, B, Sq, Sk, R, H, L.stream()))
-    assert rel_err(drel.cpu().numpy(), relt.grad.numpy()) < TOL
+    assert rel_err(drel.cpu().numpy(), rdrel.numpy()) < TOL
     # dWr/dbr sum B*Sq*Sk random-sign terms dbias/r (1/r amplified near the clamp): fp32 summation of
     # 20000 such terms against an fp64 reference carries ~1e-3 of cancellation noise
     wtol = 3e-3 if B * Sq * Sk > 5000 else TOL
-    assert rel_err(dW.cpu().numpy(), Wt.grad.numpy()) < wtol
-    assert rel_err(db.cpu().numpy(), bt.grad.numpy()) < wtol
+    assert rel_err(dW.cpu().numpy(), rdW.numpy()) < wtol
+    assert rel_err(db.cpu().numpy(), rdb.numpy()) < wtol
 
 
 @pytest.mark.parametrize('B,Sq,Sk,C,H', [(2, 7, 7, 4, 2), (2, 100, 100, 4, 8), (3, 5, 9, 3, 4), (1, 70, 3, 4, 16),
@@ -832,19 +803,13 @@ def test_attflat_pool(B, S, d, G, use_mask):
         mask = rs.uniform(size=(B, 1, 1, S)) < 0.3
         mask[0] = True                      # everything padded: softmax of equal -1e9 logits is uniform
         mask_t = torch.from_numpy(mask)
-    lt, xt = torch.from_numpy(logits).double().requires_grad_(True), torch.from_numpy(x).double().requires_grad_(True)
-    att = lt
-    if use_mask:
-        att = att.masked_fill(mask_t.squeeze(1).squeeze(1).unsqueeze(2), -1e9)
-    att = torch.softmax(att, dim=1)
-    ref = torch.cat([(att[:, :, g_:g_ + 1] * xt).sum(1) for g_ in range(G)], dim=1)
-    ref.backward(torch.from_numpy(gp).double())
+    ref, rdl, rdx, _ = attflat_pool_ref(logits, x, mask.reshape(B, S) if use_mask else None, gp)
     ld, xd = g(logits).requires_grad_(True), g(x).requires_grad_(True)
     out = ops.attflat_pool(ld, xd, mask_t.to(DEV) if use_mask else None)
     out.backward(g(gp))
-    assert rel_err(out.detach().cpu().numpy(), ref.detach().numpy()) < 1e-5
-    assert rel_err(xd.grad.cpu().numpy(), xt.grad.numpy()) < 1e-5
-    assert rel_err(ld.grad.cpu().numpy(), lt.grad.numpy()) < 2e-5
+    assert rel_err(out.detach().cpu().numpy(), ref.numpy()) < 1e-5
+    assert rel_err(xd.grad.cpu().numpy(), rdx.numpy()) < 1e-5
+    assert rel_err(ld.grad.cpu().numpy(), rdl.numpy()) < 2e-5
 
 
 # ----------------------------------------------------------------------------- attention core
