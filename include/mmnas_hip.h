@@ -420,6 +420,12 @@ int mmnas_rel_fused_bwd_ragged(const float* raw, const float* Wy, const float* b
  * Self-attention only (S x S); R = 64, C in {3,4}, H <= 32, n_ops <= MMNAS_REL_MULTI_MAX (the call loops launches of 32
  * head rows backward / 96 forward); ragged batches as mmnas_rel_fused_*_ragged (off / tile_off / ntiles, else NULL / 0).
  * ws: mmnas_rel_multi_bwd_ws_floats(B, S) floats (backward only).  Results equal the per-operator calls to round-off.
+ * key_mask (padded batches; ignored with off): the [B,S] key mask of the attention cores that consume the bias (non-zero =
+ * masked).  As for the ragged variants above, a masked key's score is replaced after the bias is added and its bias gradient
+ * is exactly zero, so with nk_b = 1 + the last unmasked key of sample b (0: all masked; masked keys below nk_b are still
+ * computed) forward writes biasT[b,h,k,q] for k < nk_b only and backward reads dbiasT there only: the rest of the planes is
+ * neither written nor read and may hold anything.  NULL, B > 256 or mmnas_set_rel_keylimit(0) / MMNAS_REL_KEYLIMIT=0: all
+ * S x S elements (the gradients then differ in summation order only).
  * ------------------------------------------------------------------------------------------ */
 #define MMNAS_REL_MULTI_MAX 32
 typedef struct mmnas_rel_multi {
@@ -434,6 +440,7 @@ typedef struct mmnas_rel_multi {
   float* dWr[MMNAS_REL_MULTI_MAX]; float* dbr[MMNAS_REL_MULTI_MAX];   /* bwd: accumulated (+=) */
   const int* off; const int* tile_off; int ntiles, reserved;          /* ragged batches (device arrays [B+1]) or NULL */
   float* ws;
+  const unsigned char* key_mask;    /* [B,S] non-zero = masked key, or NULL: all S x S elements */
 } mmnas_rel_multi;
 int mmnas_rel_multi_supported(int C, int R, int H);
 size_t mmnas_rel_multi_bwd_ws_floats(int B, int S);   /* host only */
@@ -443,6 +450,8 @@ int mmnas_rel_multi_bwd(const mmnas_rel_multi* m, void* stream);
  * entry, backward behind the last relation operator of a stream.  mmnas_set_rel_hoist(0) / MMNAS_REL_HOIST=0 restores one
  * mmnas_rel_fused_* launch per operator (A/B runs); returns the previous setting. */
 int mmnas_set_rel_hoist(int on);
+/* The key-limited walk of mmnas_rel_multi_fwd / _bwd (key_mask above); on by default; returns the previous setting. */
+int mmnas_set_rel_keylimit(int on);
 /* Likewise the key / value projections of a chain's guided operators (all read the final language state; GuidedAtt,
  * modules.py:313-325): forward as grouped launches behind the encoder, backward (key / value source gradient, dWk, dWv) as
  * grouped gradient-pair launches behind the last guided operator.  MMNAS_GUIDED_HOIST=0 / mmnas_set_guided_hoist(0): one

@@ -133,7 +133,7 @@ class RelMulti(C.Structure):
                 ('raw', _fp), ('Wy', _fp), ('by', _fp), ('dWy', _fp), ('dby', _fp),
                 ('Wr', _fp * REL_MULTI_MAX), ('br', _fp * REL_MULTI_MAX), ('biasT', _fp * REL_MULTI_MAX),
                 ('dbiasT', _fp * REL_MULTI_MAX), ('dWr', _fp * REL_MULTI_MAX), ('dbr', _fp * REL_MULTI_MAX),
-                ('off', _fp), ('tile_off', _fp), ('ntiles', C.c_int), ('reserved', C.c_int), ('ws', _fp)]
+                ('off', _fp), ('tile_off', _fp), ('ntiles', C.c_int), ('reserved', C.c_int), ('ws', _fp), ('key_mask', _fp)]
 
 
 class ProfStat(C.Structure):
@@ -215,6 +215,7 @@ SYMBOLS = {
     'mmnas_rel_multi_fwd': (_i, [C.POINTER(RelMulti), _fp]),
     'mmnas_rel_multi_bwd': (_i, [C.POINTER(RelMulti), _fp]),
     'mmnas_set_rel_hoist': (_i, [_i]),
+    'mmnas_set_rel_keylimit': (_i, [_i]),
     'mmnas_set_guided_hoist': (_i, [_i]),
     'mmnas_set_rel_overlap': (_i, [_i]),
     'mmnas_mha_core_fwd': (_i, [C.POINTER(MhaDesc), _fp]),

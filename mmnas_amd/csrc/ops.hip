@@ -831,7 +831,12 @@ struct RelGroups {
   RelGroups() { memset(hoisted, 0, sizeof(hoisted)); }
 };
 // Which operators take part: attention operators with MMNAS_F_REL | MMNAS_F_RELRAW whose shape relmulti.hip covers; backward
-// (bwd = true) only the differentiated ones.  Operators of one stream that share (raw, Wy, by, H, C) form a group.
+// (bwd = true) only the differentiated ones.  Operators of one stream that share (raw, Wy, by, H, C) and the key mask form
+// a group.  The mask is the one the operators' attention cores apply (att_core_desc): every core that reads a hoisted biasT --
+// mha_fwd_kernel / mha_fwd_pair_kernel, mha_fwd_b16_kernel / mha_fwd_b16_two_kernel, mha_bwd_q_kernel, mha_bwd_kv_kernel,
+// mha_bwd_fused_kernel, mha_bwd_b16_kernel -- adds the bias and then SELECTS -1e9 under a masked key (no arithmetic on the sum, the row maximum is
+// taken behind the select), and every backward core writes the bias gradient there as a literal 0: the relation kernels
+// leave the planes under the masked tail keys of a padded batch unwritten forward and unread backward (relmulti.hip).
 static void chain_rel_groups(const mmnas_chain* c, const ChainLayout& L, bool bwd, RelGroups& G) {
   if (!rel_hoist_on() || c->use_side_stream) return;
   char* base = (char*)c->arena;
@@ -848,14 +853,16 @@ static void chain_rel_groups(const mmnas_chain* c, const ChainLayout& L, bool bw
     const AttLayout al_ = att_layout(&a);
     std::vector<mmnas_rel_multi>& gs = G.groups[o.on_y ? 1 : 0];
     mmnas_rel_multi* g = nullptr;
+    const unsigned char* const kmask = (a.flags & MMNAS_F_MASK) ? (const unsigned char*)a.mask : nullptr;
     for (auto& q : gs)
-      if (q.raw == a.rel && q.Wy == a.Wy && q.by == a.by && q.H == a.H && q.C == a.C && q.n_ops < MMNAS_REL_MULTI_MAX) { g = &q; break; }
+      if (q.raw == a.rel && q.Wy == a.Wy && q.by == a.by && q.H == a.H && q.C == a.C && q.key_mask == kmask && q.n_ops < MMNAS_REL_MULTI_MAX) { g = &q; break; }
     if (!g) {
       mmnas_rel_multi q;
       memset(&q, 0, sizeof(q));
       q.B = a.B; q.S = a.Sq; q.C = a.C; q.R = a.R; q.H = a.H;
       q.raw = a.rel; q.Wy = a.Wy; q.by = a.by; q.dWy = a.dWy; q.dby = a.dby;
       q.off = a.q_off; q.tile_off = a.rel_tile_off; q.ntiles = a.rel_ntiles;
+      q.key_mask = kmask;
       q.ws = (float*)(base + L.relws);
       gs.push_back(q);
       g = &gs.back();

@@ -19,7 +19,10 @@
 //   then one reduction launch scatters the workgroups' partial rows into every operator's dWr / dbr and the shared dWy / dby.
 // Algorithmic work per element (fwd): 2 R (C + 1) + 2 R rows flop; bytes 4 (C + rows).  Bound: MFMA (fp32, 157 TF/s); the
 // [B, S, S, 64] relation tensor never exists (as in relfused.hip).  Ragged batches (valid n_b x n_b corner per sample)
-// walk the same tile table as mmnas_rel_fused_bwd_ragged.
+// walk the same tile table as mmnas_rel_fused_bwd_ragged.  Padded batches with a key mask walk, of every sample's
+// [S_k, S_q] plane, only the nk_b S elements under keys up to the last unmasked one (rm_key_table below): the attention
+// cores replace the score under a masked key after adding the bias and write its bias gradient as exactly 0, so nothing
+// reads the rest forward and it adds nothing backward (MMNAS_REL_KEYLIMIT=0 restores the walk over all B S^2 elements).
 #include <stdlib.h>
 #include <string.h>
 #include "common.h"
@@ -37,6 +40,7 @@ constexpr int RM_ROWS = 32;     // head rows per row tile = one MFMA tile
 constexpr int RM_NT_MAX = 3;    // row tiles per forward launch
 constexpr int RM_LDH = RM_R + 4;        // LDS row stride of the hid / dhid image
 constexpr int RM_LDP = RM_ROWS + 4;     // LDS row stride of the dpre image
+constexpr int RM_KB_MAX = 256;  // samples the key-limit table covers (2 KB of LDS); a larger batch walks densely
 constexpr int RM_ROW = RM_ROWS * RM_R + RM_R * RM_CP + RM_ROWS;   // partial row: [dWr_all 32 x 64 | dWy_ext 64 x 8 | dbr_all 32]
 
 struct RelMultiK {
@@ -44,50 +48,100 @@ struct RelMultiK {
   int B, S, C, H, nrows, nops;
   int dbg;                               // timing experiments only, in a -DMMNAS_DBG_REL=1 build (MMNAS_REL_MULTI_DBG): 1 no stores, 2 no raw reloads, 4 no head-projection MFMAs
   const int* off; const int* toff;       // ragged batches (see relfused.hip); NULL = all S x S elements
+  const unsigned char* kmask;            // padded batches: key mask [B, S] (non-zero = masked) -> key-limited walk; NULL = dense
   float* part;                           // backward: partial rows [grid][RM_ROW]
   const float* Wr[MMNAS_REL_MULTI_MAX];  // per operator of this launch: linear_r.weight [H, 64], .bias [H]
   const float* br[MMNAS_REL_MULTI_MAX];
   float* io[RM_NT_MAX * RM_ROWS];        // per ROW: forward biasT_n + h S^2 (written) / backward dbiasT_n + h S^2 (read)
 };
 
-// tile T of the whole batch -> sample and tile inside it (ragged); sample = B when T lies behind the last tile
-__device__ __forceinline__ void rm_locate(const RelMultiK& p, int T, int ntiles, int& b, int& tb) {
-  if (T >= ntiles) { b = p.B; tb = 0; return; }
-  int lo = 0, hi = p.B;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (p.toff[mid] <= T) lo = mid; else hi = mid;
+// Key-limited walk: lim[b] = nk_b S, the elements of sample b's plane that are walked, nk_b = 1 + the index of the last
+// unmasked key (0: every key masked; the mask need not be a prefix -- masked keys below nk_b are simply computed);
+// toff[b] = prefix sums of ceil(lim[b] / 32), the tile table rm_locate searches, toff[B] = the tiles to walk.  Every
+// workgroup builds both in LDS from the mask: groups of tps lanes scan one sample's keys each, wave 0 forms the sums.
+__device__ __forceinline__ void rm_key_table(const RelMultiK& p, unsigned* lim, int* toff) {
+  const int tid = threadIdx.x, B = p.B, S = p.S;
+  int tps = 64;
+  while (tps > 1 && tps * B > 256) tps >>= 1;
+  const int b = tid / tps, c = tid - b * tps;
+  int last = 0;
+  if (b < B) {
+    const unsigned char* __restrict__ row = p.kmask + (size_t)b * S;
+    if ((((size_t)p.kmask | (size_t)S) & 3) == 0) {      // four keys per load (key 4 j + i in byte i)
+      const unsigned* __restrict__ row4 = reinterpret_cast<const unsigned*>(row);
+#pragma unroll 8
+      for (int j = c; j < (S >> 2); j += tps) {
+        const unsigned v = row4[j];
+        const int hi = !(v >> 24) ? 4 : !(v & 0xff0000u) ? 3 : !(v & 0xff00u) ? 2 : !(v & 0xffu) ? 1 : 0;
+        last = hi ? 4 * j + hi : last;
+      }
+    } else {
+#pragma unroll 8
+      for (int k = c; k < S; k += tps) last = row[k] ? last : k + 1;
+    }
   }
-  b = lo; tb = T - p.toff[lo];
+  for (int d = 1; d < tps; d <<= 1) last = max(last, __shfl_xor(last, d, 64));
+  if (b < B && c == 0) lim[b] = (unsigned)last * (unsigned)S;
+  __syncthreads();
+  if (tid < 64) {      // lane l: samples 4 l .. 4 l + 3
+    int t[4], s = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { const int bb = 4 * tid + i; t[i] = bb < B ? (int)((lim[bb] + 31u) >> 5) : 0; s += t[i]; }
+    int run = s;
+    for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(run, d, 64); if (tid >= d) run += o; }
+    run -= s;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { const int bb = 4 * tid + i; run += t[i]; if (bb < B) toff[bb + 1] = run; }
+    if (tid == 0) toff[0] = 0;
+  }
+  __syncthreads();
 }
 
-// Walks the tiles of one wave: tile t covers the flattened elements f = 32 tb + lane&31 of sample b, f = k * S + q (dense)
-// or k * n_b + q over the valid corner (ragged).  elem() gives this lane's element of the current tile.
+// tile T of the whole batch -> sample and tile inside it (ragged / key-limited: toff = prefix sums of the samples' tile
+// counts); sample = B when T lies behind the last tile
+__device__ __forceinline__ void rm_locate(const int* toff, int B, int T, int ntiles, int& b, int& tb) {
+  if (T >= ntiles) { b = B; tb = 0; return; }
+  int lo = 0, hi = B;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (toff[mid] <= T) lo = mid; else hi = mid;
+  }
+  b = lo; tb = T - toff[lo];
+}
+
+// Walks the tiles of one wave: tile t covers the flattened elements f = 32 tb + lane&31 of sample b, f = k * S + q (dense;
+// key-limited: f < nk_b S) or k * n_b + q over the valid corner (ragged).  elem() gives this lane's element of the current
+// tile.  ktoff: the workgroup's LDS table of rm_key_table (read only with p.kmask).
 struct RmWalk {
   int tile, ntiles, nwaves, tpb, cb, ct, adv_b, adv_t;
-  __device__ __forceinline__ void init(const RelMultiK& p, int ntiles_, int tpb_, int w) {
+  __device__ __forceinline__ void locate(const RelMultiK& p, const int* ktoff) {
+    if (p.kmask) rm_locate(ktoff, p.B, tile, ntiles, cb, ct);
+    else if (p.toff) rm_locate(p.toff, p.B, tile, ntiles, cb, ct);
+  }
+  __device__ __forceinline__ void init(const RelMultiK& p, const int* ktoff, int ntiles_, int tpb_, int w) {
     ntiles = ntiles_; tpb = tpb_;
     nwaves = (int)gridDim.x * 4;
     adv_b = nwaves / tpb; adv_t = nwaves - adv_b * tpb;
     tile = (int)blockIdx.x * 4 + w;
     cb = tile / tpb; ct = tile - cb * tpb;
-    if (p.toff) rm_locate(p, tile, ntiles, cb, ct);
+    locate(p, ktoff);
   }
-  __device__ __forceinline__ void next(const RelMultiK& p) {
+  __device__ __forceinline__ void next(const RelMultiK& p, const int* ktoff) {
     tile += nwaves;
     cb += adv_b; ct += adv_t;
     if (ct >= tpb) { ct -= tpb; ++cb; }
-    if (p.toff) rm_locate(p, tile, ntiles, cb, ct);
+    locate(p, ktoff);
   }
 };
 
 struct RmElem { bool ok; int b; unsigned k, q, fc; };
 
-__device__ __forceinline__ RmElem rm_elem(const RelMultiK& p, int b, int tb, int l31) {
+__device__ __forceinline__ RmElem rm_elem(const RelMultiK& p, const unsigned* klim, int b, int tb, int l31) {
   RmElem e;
   const unsigned S = (unsigned)p.S, SS = S * S;
   const unsigned f = (unsigned)tb * 32u + (unsigned)l31;
   bool ok = b < p.B && f < SS;
+  if (p.kmask) ok = b < p.B && f < klim[b < p.B ? b : 0];     // key-limited: dense indexing, the plane ends at nk_b S
   unsigned wq = S;
   if (p.off) {
     const int bb = b < p.B ? b : 0;
@@ -173,14 +227,17 @@ __global__ void __launch_bounds__(256) rel_multi_fwd_kernel(const RelMultiK p, i
   __shared__ float sWrA[NT * RM_ROWS * RM_R];
   __shared__ __attribute__((aligned(16))) float sBr[NT * RM_ROWS];
   __shared__ __attribute__((aligned(16))) float* sIo[NT * RM_ROWS];
+  __shared__ unsigned sKlim[RM_KB_MAX];
+  __shared__ int sKtoff[RM_KB_MAX + 1];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l31 = lane & 31, hh = lane >> 5;
+  if (p.kmask) { rm_key_table(p, sKlim, sKtoff); ntiles = sKtoff[p.B]; }
   rm_stage_weights<false>(p, NT, sWrA, nullptr, sBr, sIo);
   float wyA[2][4];
   rm_wy_operand<C>(Wy, by, l31, hh, wyA);
   const unsigned SS = (unsigned)p.S * (unsigned)p.S;
   RmWalk wk;
-  wk.init(p, ntiles, tpb, w);
-  RmElem cur = rm_elem(p, wk.cb, wk.ct, l31);
+  wk.init(p, sKtoff, ntiles, tpb, w);
+  RmElem cur = rm_elem(p, sKlim, wk.cb, wk.ct, l31);
   f32x8 ext = rm_raw<C>(p, cur);
   while (wk.tile < ntiles) {
     f32x16 hid[2];
@@ -195,8 +252,8 @@ __global__ void __launch_bounds__(256) rel_multi_fwd_kernel(const RelMultiK p, i
     }
     const bool ok = cur.ok;
     const unsigned eoff = (unsigned)cur.b * (unsigned)p.H * SS + cur.fc;   // (host: B H S^2 < 2^31)
-    wk.next(p);
-    cur = rm_elem(p, wk.cb, wk.ct, l31);
+    wk.next(p, sKtoff);
+    cur = rm_elem(p, sKlim, wk.cb, wk.ct, l31);
     if (!RM_DBG(2)) ext = rm_raw<C>(p, cur);         // the next tile's raw row: in flight during this tile's MFMA chain
 #pragma unroll
     for (int rt = 0; rt < NT; ++rt) {
@@ -234,8 +291,11 @@ __global__ void __launch_bounds__(256, 2) rel_multi_bwd_kernel(const RelMultiK p
   __shared__ float sWrB[RM_ROWS * RM_R];
   __shared__ __attribute__((aligned(16))) float sBr[RM_ROWS];
   __shared__ __attribute__((aligned(16))) float* sIo[RM_ROWS];
+  __shared__ unsigned sKlim[RM_KB_MAX];
+  __shared__ int sKtoff[RM_KB_MAX + 1];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l31 = lane & 31, hh = lane >> 5;
   const int l15 = lane & 15, q4 = lane >> 4;
+  if (p.kmask) { rm_key_table(p, sKlim, sKtoff); ntiles = sKtoff[p.B]; }
   float* sHid = sHidAll[w];
   float* sDpre = sDpreAll[w];
   float* sRaw = sRawAll[w];
@@ -268,8 +328,8 @@ __global__ void __launch_bounds__(256, 2) rel_multi_bwd_kernel(const RelMultiK p
       }
   };
   RmWalk wk;
-  wk.init(p, ntiles, tpb, w);
-  RmElem cur = rm_elem(p, wk.cb, wk.ct, l31);
+  wk.init(p, sKtoff, ntiles, tpb, w);
+  RmElem cur = rm_elem(p, sKlim, wk.cb, wk.ct, l31);
   float db[16];
   f32x8 ext = rm_raw<C>(p, cur);
   load_db(cur, db);
@@ -326,8 +386,8 @@ __global__ void __launch_bounds__(256, 2) rel_multi_bwd_kernel(const RelMultiK p
       *reinterpret_cast<float4*>(sRaw + l31 * RM_CP + 4) = make_float4(ext[4], ext[5], ext[6], ext[7]);
     }
     // the next tile's raw row and bias gradients: into the registers this tile is done with, in flight during steps 4-5
-    wk.next(p);
-    cur = rm_elem(p, wk.cb, wk.ct, l31);
+    wk.next(p, sKtoff);
+    cur = rm_elem(p, sKlim, wk.cb, wk.ct, l31);
     ext = rm_raw<C>(p, cur);
     load_db(cur, db);
     // 4. gradient of the hidden layer, summed over every operator's heads, gated by relu'
@@ -488,6 +548,10 @@ static int rm_check(const mmnas_rel_multi* m, const char* who) {
 }
 
 static long rm_tiles_per_b(int S) { return ((long)S * S + 31) / 32; }
+// the key mask the kernels walk by: padded batches of at most RM_KB_MAX samples, unless MMNAS_REL_KEYLIMIT=0
+static const unsigned char* rm_key_mask(const mmnas_rel_multi* m) {
+  return (m->key_mask && !m->off && m->B <= RM_KB_MAX && sw::rel_keylimit.get()) ? m->key_mask : nullptr;
+}
 static int rm_grid(long ntiles, int per_cu) {
   const long wgs = (ntiles + 3) / 4, cap = 256l * per_cu;
   return (int)(wgs < 1 ? 1 : (wgs < cap ? wgs : cap));
@@ -496,6 +560,8 @@ static int rm_grid(long ntiles, int per_cu) {
 }  // namespace mmnas
 
 using namespace mmnas;
+
+extern "C" int mmnas_set_rel_keylimit(int on) { return sw::rel_keylimit.set(on != 0); }
 
 extern "C" int mmnas_rel_multi_supported(int C, int R, int H) { return R == RM_R && (C == 3 || C == 4) && H >= 1 && H <= RM_ROWS && RM_ROWS % H == 0; }
 
@@ -518,6 +584,7 @@ extern "C" int mmnas_rel_multi_fwd(const mmnas_rel_multi* m, void* stream) {
     RelMultiK k;
     memset(&k, 0, sizeof(k));
     k.raw = m->raw; k.B = m->B; k.S = m->S; k.C = m->C; k.H = m->H; k.off = m->off; k.toff = m->tile_off;
+    k.kmask = rm_key_mask(m);
     k.dbg = sw::rel_multi_dbg.get();
     // rows: operator j of this launch holds rows j H .. j H + H - 1 (H divides 32: no operator straddles two row tiles)
     for (int j = 0; j < n; ++j) {
@@ -561,6 +628,7 @@ extern "C" int mmnas_rel_multi_bwd(const mmnas_rel_multi* m, void* stream) {
     memset(&k, 0, sizeof(k));
     memset(&red, 0, sizeof(red));
     k.raw = m->raw; k.B = m->B; k.S = m->S; k.C = m->C; k.H = m->H; k.off = m->off; k.toff = m->tile_off;
+    k.kmask = rm_key_mask(m);
     k.part = m->ws; k.nops = n; k.nrows = n * m->H;
     for (int j = 0; j < n; ++j) {
       MMNAS_REQUIRE(m->Wr[o0 + j] && m->br[o0 + j] && m->dbiasT[o0 + j] && m->dWr[o0 + j] && m->dbr[o0 + j], MMNAS_E_ARG,

@@ -69,6 +69,7 @@ struct Switch {
   X(rel_multi_dbg, "MMNAS_REL_MULTI_DBG", 0, int, once, "timing experiments of a -DMMNAS_DBG_REL=1 build only (wrong results): 1 no stores, 2 no raw reloads, 4 no head-projection MFMAs") \
   X(rel_multi_wgs, "MMNAS_REL_MULTI_WGS", 3, int, once, "workgroups per CU of the multi-operator relation forward (tuning)") \
   X(rel_multi_yield, "MMNAS_REL_MULTI_YIELD", 0, int, once, "1 | 3: the multi-operator relation kernels' yield variants (tuning)") \
+  X(rel_keylimit, "MMNAS_REL_KEYLIMIT", 1, int, once, "multi-operator relation kernels of a padded batch walk only the elements under keys up to each sample's last unmasked one (mmnas_set_rel_keylimit); 0: all B S^2 elements") \
   X(rel_bwd_valu, "MMNAS_REL_BWD_VALU", 1, bool, once, "0: the fused relation backward as the all-MFMA kernel (A/B)") \
   /* gemm.hip: tuning, read by load_tuning() */ \
   X(gemm_tile, "MMNAS_GEMM_TILE", 0, int, reload, "64 | 128: force the tile shape") \
