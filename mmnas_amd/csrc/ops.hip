@@ -17,6 +17,8 @@
 namespace mmnas {
 
 static inline size_t al(size_t n) { return (n + 255) & ~(size_t)255; }
+// whether this operator (or the head) drops: training mode with a positive rate
+template <class Op> static inline bool drops(const Op* op) { return (op->flags & MMNAS_F_TRAIN) && op->drop_p > 0.f; }
 
 struct Carver {
   char* base; size_t off;
@@ -42,7 +44,7 @@ static AttLayout att_layout(const mmnas_att_op* op) {
   L.Mq = op->q_off ? (size_t)op->Mq : (size_t)op->B * op->Sq;     // (packed rows: the sum of the sequences' lengths)
   L.Mk = op->k_off ? (size_t)op->Mk : (size_t)op->B * op->Sk;
   const bool norm = op->flags & MMNAS_F_NORM, rel = op->flags & MMNAS_F_REL;
-  const bool drop = (op->flags & MMNAS_F_TRAIN) && op->drop_p > 0.f;
+  const bool drop = drops(op);
   Carver s(op->save);
   L.Q = s.take(L.Mq * op->di); L.K = s.take(L.Mk * op->di); L.V = s.take(L.Mk * op->di);
   L.att = s.take(L.Mq * op->di);
@@ -71,6 +73,23 @@ int ffn_small_fwd(const mmnas_mlp_op* op, float* h, float* z, hipStream_t st);
 bool sa_small_bwd_applies(const mmnas_att_op* op);
 int sa_small_bwd(const mmnas_att_op* op, const float* Q, const float* K, const float* V, const float* stats, const float* z,
                  float* dt_out, float* dQ, float* dK, float* dV, float* lnpart, hipStream_t st);
+
+// Where an attention operator's LayerNorm runs: inside its own forward launch / inside its own backward launch (the one-launch
+// short-sequence kernels above), or neither (its own launch on the general path; the node's mix kernel in a mixed chain).  The ONE
+// answer for att_fwd_impl and att_bwd_impl, for what a mixed chain's node epilogue is handed (chain_cand_view, both directions) and for the node's
+// fused LayerNorm backward (chain_bwd_mixed).  Shapes, flags and switches decide, not the input pointers: sa_small_applies also
+// wants xq == xkv, which a SELF operator of a chain has by construction and which a caller may ask about before it binds
+// them; the per-operator entry points compare their own two pointers next to this.
+struct LnPlace { bool fwd, bwd; };
+static LnPlace att_ln_place(const mmnas_att_op* op) {
+  LnPlace p = {false, false};
+  if (!(op->flags & MMNAS_F_SELF) || (op->flags & MMNAS_F_REL)) return p;   // (the short-sequence kernels: plain self-attention)
+  mmnas_att_op t = *op;
+  t.xkv = t.xq;
+  p.fwd = sa_small_applies(&t);
+  p.bwd = p.fwd && sa_small_bwd_applies(&t);   // (MMNAS_SMALL_BWD=0: the one-launch forward, then the general backward)
+  return p;
+}
 
 static int att_check(const mmnas_att_op* op, const char* who) {
   MMNAS_REQUIRE(op, MMNAS_E_ARG, "%s: null descriptor", who);
@@ -136,7 +155,7 @@ static void att_qkv_groups(const mmnas_att_op* op, const AttLayout& L, mmnas_gem
 
 static void att_core_desc(const mmnas_att_op* op, const AttLayout& L, mmnas_mha_desc* m) {
   const int fl = op->flags, di = op->di;
-  const bool drop = (fl & MMNAS_F_TRAIN) && op->drop_p > 0.f;
+  const bool drop = drops(op);
   memset(m, 0, sizeof(*m));
   m->B = op->B; m->H = op->H; m->Sq = op->Sq; m->Sk = op->Sk; m->dh = op->dh;
   m->ldq = m->ldk = m->ldv = m->ldo = di;
@@ -213,10 +232,10 @@ static int mmnas::att_fwd_impl(const mmnas_att_op* op, void* stream, bool defer_
   if (rc) return rc;
   const int fl = op->flags;
   const bool norm = fl & MMNAS_F_NORM;
-  const bool drop = (fl & MMNAS_F_TRAIN) && op->drop_p > 0.f;
+  const bool drop = drops(op);
   AttLayout L = att_layout(op);
   const int d = op->d, di = op->di;
-  if (sa_small_applies(op)) return sa_small_fwd(op, L.Q, L.K, L.V, L.att, L.stats, L.z, (hipStream_t)stream);
+  if (op->xq == op->xkv && att_ln_place(op).fwd) return sa_small_fwd(op, L.Q, L.K, L.V, L.att, L.stats, L.z, (hipStream_t)stream);
 
   mmnas_gemm_desc g;
   gemm_init(g, MMNAS_GEMM_NT, di, d, d, d, di);
@@ -283,7 +302,7 @@ static int att_bwd_impl(const mmnas_att_op* op, hipStream_t stream, SideQueue* s
                 MMNAS_E_ARG, "att_op_bwd: null pointer");
   const int fl = op->flags;
   const bool norm = fl & MMNAS_F_NORM, rel = fl & MMNAS_F_REL, self = fl & MMNAS_F_SELF;
-  const bool drop = (fl & MMNAS_F_TRAIN) && op->drop_p > 0.f;
+  const bool drop = drops(op);
   if (!self) MMNAS_REQUIRE(op->dxkv, MMNAS_E_ARG, "att_op_bwd: dxkv required unless SELF");
   if (norm) MMNAS_REQUIRE(op->ln_a && op->dln_a && op->dln_b, MMNAS_E_ARG, "att_op_bwd: NORM gradients missing");
   if (rel) MMNAS_REQUIRE(op->rel && op->Wr && op->br && op->dWr && op->dbr, MMNAS_E_ARG, "att_op_bwd: REL gradients missing");
@@ -292,7 +311,7 @@ static int att_bwd_impl(const mmnas_att_op* op, hipStream_t stream, SideQueue* s
 
   // Short sequences (the language stream): steps 1, 2, 4 and the data-gradient half of 5 + 6 as ONE launch (small.hip), then
   // the four weight gradients as one grouped launch that carries the LayerNorm parameter reduction.
-  if (!ln_pre && !sq && self && !rel && sa_small_bwd_applies(op)) {
+  if (!ln_pre && !sq && op->xq == op->xkv && att_ln_place(op).bwd) {
     float* const dt_out = drop ? L.dt : (norm ? L.dz : nullptr);
     if ((rc = sa_small_bwd(op, L.Q, L.K, L.V, L.stats, L.z, dt_out, L.dQ, L.dK, L.dV, norm ? L.lnws : nullptr, stream))) return rc;
     mmnas_gemm_desc w4;
@@ -340,14 +359,8 @@ static int att_bwd_impl(const mmnas_att_op* op, hipStream_t stream, SideQueue* s
 
   // 4. attention core backward
   mmnas_mha_desc m;
-  memset(&m, 0, sizeof(m));
-  m.B = op->B; m.H = op->H; m.Sq = op->Sq; m.Sk = op->Sk; m.dh = op->dh;
-  m.ldq = m.ldk = m.ldv = m.ldo = di;
-  m.Q = L.Q; m.K = L.K; m.V = L.V; m.mask = (fl & MMNAS_F_MASK) ? op->mask : nullptr; m.biasT = L.biasT;
-  m.O = L.att; m.lse = L.stats;
-  m.drop_p = drop ? op->drop_p : 0.f; m.drop_site = 0; m.drop_seed = op->seed;
+  att_core_desc(op, L, &m);
   m.dO = L.datt; m.dQ = L.dQ; m.dK = L.dK; m.dV = L.dV; m.dbiasT = L.dbiasT; m.delta = L.delta;
-  m.q_off = op->q_off; m.k_off = op->k_off;
   if ((rc = mmnas_mha_core_bwd(&m, stream))) return rc;
 
   // 5. + 6. projection weight gradients and input gradients (+ the residual branch dz), pairwise in one launch
@@ -445,7 +458,7 @@ struct MlpLayout {
 static MlpLayout mlp_layout(const mmnas_mlp_op* op) {
   MlpLayout L;
   const bool norm = op->flags & MMNAS_F_NORM;
-  const bool drop = (op->flags & MMNAS_F_TRAIN) && op->drop_p > 0.f;
+  const bool drop = drops(op);
   const size_t M = (size_t)op->M;
   Carver s(op->save);
   L.h[0] = nullptr;
@@ -504,7 +517,7 @@ static int mmnas::mlp_fwd_impl(const mmnas_mlp_op* op, void* stream, bool defer_
   MMNAS_REQUIRE(op->x && op->y && op->save, MMNAS_E_ARG, "mlp_op_fwd: null pointer");
   const int fl = op->flags;
   const bool norm = fl & MMNAS_F_NORM;
-  const bool drop = (fl & MMNAS_F_TRAIN) && op->drop_p > 0.f;
+  const bool drop = drops(op);
   if (norm) MMNAS_REQUIRE(op->ln_a && op->ln_b, MMNAS_E_ARG, "mlp_op_fwd: NORM without ln parameters");
   MlpLayout L = mlp_layout(op);
   const int d = op->dims[0];
@@ -543,7 +556,7 @@ static int mlp_bwd_impl(const mmnas_mlp_op* op, hipStream_t stream, SideQueue* s
   MMNAS_REQUIRE(op->x && op->save && op->ws && op->dy && op->dx, MMNAS_E_ARG, "mlp_op_bwd: null pointer");
   const int fl = op->flags;
   const bool norm = fl & MMNAS_F_NORM;
-  const bool drop = (fl & MMNAS_F_TRAIN) && op->drop_p > 0.f;
+  const bool drop = drops(op);
   MlpLayout L = mlp_layout(op);
   const int d = op->dims[0], M = op->M, nl = op->nl;
   for (int i = 0; i < nl; ++i)
@@ -639,6 +652,9 @@ struct ChainLayout {
       tmp[MMNAS_CHAIN_MAX_OPS];
   size_t dpre, encdy, relws, total;
   int last_x, last_y, first_x, first_y, n_guided;
+  // per operator: the operator (mixed chains: the node, named by its first operator) whose output it reads, -1 = the chain's
+  // input; the node it belongs to (plain chains: itself)
+  int src[MMNAS_CHAIN_MAX_OPS], head[MMNAS_CHAIN_MAX_OPS];
   // mixed chains: per node (indexed by the node's first operator) the node output and the sampled candidate's output
   // gradient; one scratch block for the gate-gradient partials
   size_t nout[MMNAS_CHAIN_MAX_OPS], ndact[MMNAS_CHAIN_MAX_OPS], mixws;
@@ -685,8 +701,9 @@ static int chain_check(const mmnas_chain* c, const char* who) {
 // rows of the decoder stream: B * Sy, or the packed row count of a ragged batch
 static inline size_t chain_rows_y(const mmnas_chain* c) { return c->y_off ? (size_t)c->Ny : (size_t)c->B * c->Sy; }
 
-// operator i with its stream-dependent fields filled in (shapes, masks, relation tensors); buffers come later
-static void chain_op_setup(const mmnas_chain* c, int i, mmnas_att_op& a, mmnas_mlp_op& m) {
+// operator i with its stream-dependent fields filled in (shapes, masks, relation tensors): all that chain_layout, which runs
+// before an arena exists, needs; the buffers come with chain_bind
+static void chain_op_shapes(const mmnas_chain* c, int i, mmnas_att_op& a, mmnas_mlp_op& m) {
   const mmnas_chain_op& o = c->ops[i];
   const int S = o.on_y ? c->Sy : c->Sx;
   if (o.kind == MMNAS_CHAIN_ATT) {
@@ -714,7 +731,11 @@ static int chain_layout(const mmnas_chain* c, ChainLayout& L) {
   auto take = [&](size_t bytes) { size_t r = off; off += al(bytes); return r; };
   L.last_x = L.last_y = L.first_x = L.first_y = -1;
   L.n_guided = 0;
+  int cur[2] = {-1, -1}, head = 0;   // per stream: who wrote its current state
   for (int i = 0; i < c->n_ops; ++i) {
+    if (i > 0 && (!c->mixed || c->ops[i].node != c->ops[i - 1].node)) { cur[c->ops[head].on_y ? 1 : 0] = head; head = i; }
+    L.head[i] = head; L.src[i] = cur[c->ops[i].on_y ? 1 : 0];
+    if (head != i) continue;   // (mixed chains: the streams' first / last markers refer to NODES, the first operator of each)
     if (c->ops[i].on_y) { if (L.first_y < 0) L.first_y = i; L.last_y = i; }
     else { if (L.first_x < 0) L.first_x = i; L.last_x = i; }
   }
@@ -722,7 +743,7 @@ static int chain_layout(const mmnas_chain* c, ChainLayout& L) {
   for (int i = 0; i < c->n_ops; ++i) {
     const mmnas_chain_op& o = c->ops[i];
     mmnas_att_op a; mmnas_mlp_op m;
-    chain_op_setup(c, i, a, m);
+    chain_op_shapes(c, i, a, m);
     mmnas_plan pl;
     int rc = o.kind == MMNAS_CHAIN_ATT ? mmnas_att_op_plan(&a, &pl) : mmnas_mlp_op_plan(&m, &pl);
     if (rc) return rc;
@@ -740,26 +761,97 @@ static int chain_layout(const mmnas_chain* c, ChainLayout& L) {
   L.relws = take(mmnas_rel_multi_bwd_ws_floats(c->B, c->Sx > c->Sy ? c->Sx : c->Sy) * sizeof(float));
   L.mixws = 0;
   if (c->mixed) {
+    int nodes = 0;
     for (int i = 0; i < c->n_ops; ++i) {
-      const bool first = i == 0 || c->ops[i].node != c->ops[i - 1].node;
+      const bool first = L.head[i] == i;
       L.nout[i] = first ? take(c->ops[i].on_y ? ny : nx) : 0;
       L.ndact[i] = first ? take(c->ops[i].on_y ? ny : nx) : 0;
+      nodes += first;
     }
-    {   // one partial-sum area per node: the gate-gradient reductions of the backward are issued as ONE launch at its end
-      int nodes = 0;
-      for (int i = 0; i < c->n_ops; ++i) nodes += (i == 0 || c->ops[i].node != c->ops[i - 1].node);
-      L.mixws = take((size_t)(nodes > 0 ? nodes : 1) * mmnas_mixed_sum_ws_floats() * sizeof(float));
-    }
-    // (streams' first / last markers refer to NODES here: the first operator of the first / last node of a stream)
-    L.last_x = L.last_y = L.first_x = L.first_y = -1;
-    for (int i = 0; i < c->n_ops; ++i) {
-      if (!(i == 0 || c->ops[i].node != c->ops[i - 1].node)) continue;
-      if (c->ops[i].on_y) { if (L.first_y < 0) L.first_y = i; L.last_y = i; }
-      else { if (L.first_x < 0) L.first_x = i; L.last_x = i; }
-    }
+    // one partial-sum area per node: the gate-gradient reductions of the backward are issued as ONE launch at its end
+    L.mixws = take((size_t)(nodes > 0 ? nodes : 1) * mmnas_mixed_sum_ws_floats() * sizeof(float));
   }
   L.total = off;
   return MMNAS_OK;
+}
+
+// ---- one binding of an operator to the chain ----
+// Operator i as the walkers use it: chain_op_shapes' fields, its saved block and its backward scratch from the arena and, on
+// request, the layout of the two.  What turns a per-operator ChainLayout offset into a pointer lives between here and
+// chain_bind_bwd: the walkers below name buffers by operator (mixed chains: by node = its first operator) only.
+struct BoundOp {
+  int i;
+  bool att;                        // which of a / m is the operator
+  mmnas_att_op a; mmnas_mlp_op m;
+  AttLayout al; MlpLayout ml;      // (chain_bind with layouts = true)
+  float* y;                        // the operator's own output block (plain chains: chain_out picks x_out / y_out for a stream's last)
+  int flags() const { return att ? a.flags : m.flags; }
+  float eps() const { return att ? a.eps : m.eps; }
+};
+static inline float* chain_buf(const mmnas_chain* c, size_t off) { return (float*)((char*)c->arena + off); }
+static void chain_bind(const mmnas_chain* c, const ChainLayout& L, int i, BoundOp& b, bool layouts = false) {
+  b.i = i; b.att = c->ops[i].kind == MMNAS_CHAIN_ATT;
+  chain_op_shapes(c, i, b.a, b.m);
+  b.y = chain_buf(c, L.y[i]);
+  if (b.att) { b.a.save = chain_buf(c, L.save[i]); b.a.ws = chain_buf(c, L.ws[i]); if (layouts) b.al = att_layout(&b.a); }
+  else { b.m.save = chain_buf(c, L.save[i]); b.m.ws = chain_buf(c, L.ws[i]); if (layouts) b.ml = mlp_layout(&b.m); }
+}
+// output buffer of operator i (mixed chains: of the node whose first operator is i)
+static float* chain_out(const mmnas_chain* c, const ChainLayout& L, int i) {
+  return i == L.last_x ? c->x_out : (i == L.last_y ? c->y_out : chain_buf(c, c->mixed ? L.nout[i] : L.y[i]));
+}
+// input of operator i: the previous output on its stream, or the chain's input
+static const float* chain_in(const mmnas_chain* c, const ChainLayout& L, int i) {
+  return L.src[i] >= 0 ? chain_out(c, L, L.src[i]) : (c->ops[i].on_y ? c->y_in : c->x_in);
+}
+// the FINAL language state: the key / value source of every guided operator
+static const float* chain_x_final(const mmnas_chain* c, const ChainLayout& L) { return L.last_x >= 0 ? c->x_out : c->x_in; }
+// input-gradient buffer of operator i (mixed chains: of its node, kept in the sampled candidate i's block)
+static float* chain_din(const mmnas_chain* c, const ChainLayout& L, int i) {
+  return L.head[i] == L.first_x ? c->dx_in : (L.head[i] == L.first_y ? c->dy_in : chain_buf(c, L.dx[i]));
+}
+// hoisted key / value source gradient of guided operator i; mixed chains: node i0's sampled-candidate output gradient and the
+// k-th node's partial sums of the gate gradients
+static float* chain_guided_tmp(const mmnas_chain* c, const ChainLayout& L, int i) { return chain_buf(c, L.tmp[i]); }
+static float* chain_node_dact(const mmnas_chain* c, const ChainLayout& L, int i0) { return chain_buf(c, L.ndact[i0]); }
+static float* chain_gate_ws(const mmnas_chain* c, const ChainLayout& L, int k) { return chain_buf(c, L.mixws) + (size_t)k * mmnas_mixed_sum_ws_floats(); }
+// forward pointers: the input(s) and where the output goes
+static void chain_bind_fwd(BoundOp& b, const mmnas_chain* c, const ChainLayout& L, float* out) {
+  const float* in = chain_in(c, L, b.i);
+  if (b.att) { b.a.xq = in; b.a.xkv = (b.a.flags & MMNAS_F_SELF) ? in : chain_x_final(c, L); b.a.y = out; }   // guided: keys / values from the FINAL language state
+  else { b.m.x = in; b.m.y = out; }
+}
+// backward pointers: the input(s), the output gradient, where the input gradient goes (returned)
+static float* chain_bind_bwd(BoundOp& b, const mmnas_chain* c, const ChainLayout& L, const float* dy) {
+  const float* in = chain_in(c, L, b.i);
+  float* dx = chain_din(c, L, b.i);
+  if (b.att) {
+    const bool self = b.a.flags & MMNAS_F_SELF;
+    b.a.xq = in; b.a.xkv = self ? in : chain_x_final(c, L);
+    b.a.dy = dy; b.a.dxq = dx;
+    b.a.dxkv = self ? nullptr : chain_buf(c, L.dpre);     // guided: added into the chain's running sum (zeroed by chain_bwd_begin)
+    b.a.drel = nullptr;
+  } else { b.m.x = in; b.m.dy = dy; b.m.dx = dx; }
+  return dx;
+}
+// one bound operator's launches.  Forward: *ln_done as att_fwd_impl reports it.  Backward: guided operators add into dxkv.
+static int chain_run_fwd(const BoundOp& b, hipStream_t s, bool defer_ln, bool* ln_done, bool rel_ready, bool kv_ready) {
+  return b.att ? att_fwd_impl(&b.a, s, defer_ln, ln_done, rel_ready, kv_ready) : mlp_fwd_impl(&b.m, s, defer_ln, ln_done);
+}
+static int chain_run_bwd(const BoundOp& b, hipStream_t s, SideQueue* sq, bool rel_defer, bool kv_defer, const AuxReduce* ln_pre = nullptr) {
+  return b.att ? att_bwd_impl(&b.a, s, sq, !(b.a.flags & MMNAS_F_SELF), rel_defer, kv_defer, ln_pre) : mlp_bwd_impl(&b.m, s, sq, ln_pre);
+}
+// Where candidate i's LayerNorm runs, forward and backward (att_ln_place; an MLP candidate with a LayerNorm never normalises
+// itself in a mixed chain: mlp_fwd_impl keeps the general path under defer_ln), and with it what the node epilogue reads for the
+// candidate in EITHER direction: its pre-LayerNorm sum with the LayerNorm parameters, or -- no LayerNorm, or the operator's own
+// forward normalised -- its output alone (*la = NULL).  b: bound with layouts.
+static LnPlace chain_cand_view(const BoundOp& b, const float** z, const float** la, const float** lb) {
+  LnPlace p = {false, false};
+  if (b.att) p = att_ln_place(&b.a);
+  if (!(b.flags() & MMNAS_F_NORM) || p.fwd) { *z = b.y; *la = nullptr; *lb = nullptr; }
+  else if (b.att) { *z = b.al.z; *la = b.a.ln_a; *lb = b.a.ln_b; }
+  else { *z = b.ml.z; *la = b.m.ln_a; *lb = b.m.ln_b; }
+  return p;
 }
 
 // ---- side stream + events, one set per (device, main stream) ----
@@ -839,18 +931,17 @@ struct RelGroups {
 // leave the planes under the masked tail keys of a padded batch unwritten forward and unread backward (relmulti.hip).
 static void chain_rel_groups(const mmnas_chain* c, const ChainLayout& L, bool bwd, RelGroups& G) {
   if (!rel_hoist_on() || c->use_side_stream) return;
-  char* base = (char*)c->arena;
   for (int i = 0; i < c->n_ops; ++i) {
     const mmnas_chain_op& o = c->ops[i];
     if (o.kind != MMNAS_CHAIN_ATT) continue;
     if (bwd && c->mixed && o.detached) continue;
-    mmnas_att_op a; mmnas_mlp_op m;
-    chain_op_setup(c, i, a, m);
-    if (!(a.flags & MMNAS_F_REL) || !(a.flags & MMNAS_F_RELRAW) || !(a.flags & MMNAS_F_SELF)) continue;
+    if (!(o.att.flags & MMNAS_F_REL) || !(o.att.flags & MMNAS_F_RELRAW) || !(o.att.flags & MMNAS_F_SELF)) continue;
+    BoundOp b;
+    chain_bind(c, L, i, b, true);
+    const mmnas_att_op& a = b.a;
+    const AttLayout& al_ = b.al;
     if (!mmnas_rel_multi_supported(a.C, a.R, a.H) || !a.rel || !a.Wy || !a.by) continue;
     if ((long)a.B * a.H * a.Sq * a.Sq >= (1l << 31)) continue;
-    a.save = base + L.save[i]; a.ws = base + L.ws[i];
-    const AttLayout al_ = att_layout(&a);
     std::vector<mmnas_rel_multi>& gs = G.groups[o.on_y ? 1 : 0];
     mmnas_rel_multi* g = nullptr;
     const unsigned char* const kmask = (a.flags & MMNAS_F_MASK) ? (const unsigned char*)a.mask : nullptr;
@@ -863,7 +954,7 @@ static void chain_rel_groups(const mmnas_chain* c, const ChainLayout& L, bool bw
       q.raw = a.rel; q.Wy = a.Wy; q.by = a.by; q.dWy = a.dWy; q.dby = a.dby;
       q.off = a.q_off; q.tile_off = a.rel_tile_off; q.ntiles = a.rel_ntiles;
       q.key_mask = kmask;
-      q.ws = (float*)(base + L.relws);
+      q.ws = chain_buf(c, L.relws);
       gs.push_back(q);
       g = &gs.back();
     }
@@ -927,17 +1018,17 @@ static void chain_guided_set(const mmnas_chain* c, bool bwd, bool allow, GuidedS
   }
   if (G.n < 2) { for (int j = 0; j < G.n; ++j) G.hoisted[G.idx[j]] = false; G.n = 0; }   // (one operator: nothing to merge)
 }
-static int chain_guided_kv_fwd(const mmnas_chain* c, const ChainLayout& L, const GuidedSet& G, const float* x_final, hipStream_t st) {
-  char* base = (char*)c->arena;
+static int chain_guided_kv_fwd(const mmnas_chain* c, const ChainLayout& L, const GuidedSet& G, hipStream_t st) {
+  const float* x_final = chain_x_final(c, L);
   for (int j0 = 0; j0 < G.n; j0 += GUIDED_PER_LAUNCH) {
     const int n = G.n - j0 < GUIDED_PER_LAUNCH ? G.n - j0 : GUIDED_PER_LAUNCH;
     mmnas_gemm_desc g;
     for (int j = 0; j < n; ++j) {
       const int i = G.idx[j0 + j];
-      mmnas_att_op a; mmnas_mlp_op m;
-      chain_op_setup(c, i, a, m);
-      a.save = base + L.save[i]; a.ws = base + L.ws[i];
-      const AttLayout al_ = att_layout(&a);
+      BoundOp b;
+      chain_bind(c, L, i, b, true);
+      const mmnas_att_op& a = b.a;
+      const AttLayout& al_ = b.al;
       if (j == 0) { gemm_init(g, MMNAS_GEMM_NT, a.di, c->d, c->d, c->d, a.di); g.ngroups = 2 * n; }
       mmnas_gemm_group* gg = g.g + 2 * j;
       memset(gg, 0, 2 * sizeof(*gg));
@@ -951,9 +1042,9 @@ static int chain_guided_kv_fwd(const mmnas_chain* c, const ChainLayout& L, const
 }
 // behind the last guided operator's backward: per-operator key / value source gradients + dWk / dWv, then their sum (+ the
 // head's gradient of the language state, when there is one) into `out`
-static int chain_guided_kv_bwd(const mmnas_chain* c, const ChainLayout& L, const GuidedSet& G, const float* x_final, const float* extra,
-                               const float* extra2, float* out, hipStream_t st) {
-  char* base = (char*)c->arena;
+static int chain_guided_kv_bwd(const mmnas_chain* c, const ChainLayout& L, const GuidedSet& G, const float* extra, const float* extra2,
+                               float* out, hipStream_t st) {
+  const float* x_final = chain_x_final(c, L);
   const float* srcs[ADD_MANY_MAX + 2];
   int ns = 0;
   if (extra) srcs[ns++] = extra;
@@ -963,16 +1054,16 @@ static int chain_guided_kv_bwd(const mmnas_chain* c, const ChainLayout& L, const
     mmnas_gemm_desc g, w;
     for (int j = 0; j < n; ++j) {
       const int i = G.idx[j0 + j];
-      mmnas_att_op a; mmnas_mlp_op m;
-      chain_op_setup(c, i, a, m);
-      a.save = base + L.save[i]; a.ws = base + L.ws[i];
-      const AttLayout al_ = att_layout(&a);
+      BoundOp b;
+      chain_bind(c, L, i, b, true);
+      const mmnas_att_op& a = b.a;
+      const AttLayout& al_ = b.al;
       const int Mk = (int)al_.Mk, di = a.di, d = c->d;
       if (j == 0) {
         gemm_init(g, MMNAS_GEMM_NN, d, di, di, d, d); g.ngroups = n; g.nseg = 2;
         gemm_init(w, MMNAS_GEMM_TN, d, Mk, di, d, d); w.ngroups = 2 * n; w.accumulate = 1;
       }
-      float* tmp = (float*)(base + L.tmp[i]);
+      float* tmp = chain_guided_tmp(c, L, i);
       memset(&g.g[j], 0, sizeof(g.g[j]));
       g.g[j].M = Mk; g.g[j].C = tmp;
       g.g[j].A[0] = al_.dK; g.g[j].B[0] = a.Wk;
@@ -1006,100 +1097,177 @@ extern "C" int mmnas_chain_plan(const mmnas_chain* c, size_t* arena_bytes) {
 }
 
 namespace mmnas {
+// ---- the stream steps both walkers take: mmnas_chain_fwd / _bwd name them by operator, chain_fwd_mixed / chain_bwd_mixed by
+// node (= its first operator) ----
+// Forward, chain entry: every hoisted relation bias.  may_fork and MMNAS_REL_OVERLAP: the image stream's on the side stream
+// beside the encoder (see rel_overlap_on); *forked is then that stream's context, and the caller joins it (chain_rel_join) in
+// front of the first decoder operator / node that reads a hoisted bias.
+static int chain_rel_prologue(const mmnas_chain* c, const ChainLayout& L, const RelGroups& RG, hipStream_t st, bool may_fork, SideCtx** forked) {
+  SideCtx* rsc = (may_fork && rel_overlap_on() && !RG.groups[1].empty() && L.last_x >= 0 && L.first_y >= 0) ? side_ctx(st, true) : nullptr;
+  *forked = rsc;
+  if (!rsc) return chain_rel_fwd(RG, st);
+  int rc;
+  if ((rc = ev_fork(st, rsc->side, rsc->ovl[0]))) return rc;
+  if ((rc = chain_rel_fwd(RG, rsc->side, 1))) return rc;
+  return chain_rel_fwd(RG, st, 0);
+}
+static int chain_rel_join(SideCtx* rsc, hipStream_t st) { return ev_fork(rsc->side, st, rsc->ovl[1]); }   // the image stream's bias exists from here on
+// Forward, chain exit: a stream without operators hands its input on
+static int chain_fwd_passthrough(const mmnas_chain* c, const ChainLayout& L, hipStream_t st) {
+  const size_t nx = (size_t)c->B * c->Sx * c->d * sizeof(float), ny = chain_rows_y(c) * c->d * sizeof(float);
+  if (L.last_x < 0 && hipMemcpyAsync(c->x_out, c->x_in, nx, hipMemcpyDeviceToDevice, st) != hipSuccess) return MMNAS_E_LAUNCH;
+  if (L.last_y < 0 && hipMemcpyAsync(c->y_out, c->y_in, ny, hipMemcpyDeviceToDevice, st) != hipSuccess) return MMNAS_E_LAUNCH;
+  return MMNAS_OK;
+}
+
+// What a backward walk carries from step to step.
+struct ChainBwd {
+  const mmnas_chain* c; const ChainLayout* L;
+  hipStream_t st;       // the caller's stream
+  SideQueue* sq;        // plain chains with a side stream: the queued parameter-gradient work (else NULL)
+  RelGroups RG;         // relation operators whose bias gradient waits for the one launch behind their stream's first operator / node
+  GuidedSet GS;         // guided operators whose dK / dV wait for the grouped launches behind the first of them in chain order
+  int G;                // ... that operator: the last hoisted guided operator in backward order (-1: none)
+  float *dpre, *encdy;  // running sum of the unhoisted guided operators' key / value source gradients; the encoder's output gradient
+  size_t ex;
+  const float* enc_grad = nullptr;   // set by the hoisted launch: the encoder's output gradient, complete
+  SideCtx* rel_bwd_side = nullptr;   // set when the image stream's relation backward went to the side stream: joined below
+};
+// hoist: relation and guided hoists allowed (not under the encoder / decoder overlap of a plain chain)
+static int chain_bwd_begin(ChainBwd& S, const mmnas_chain* c, const ChainLayout& L, hipStream_t st, SideQueue* sq, bool hoist) {
+  S.c = c; S.L = &L; S.st = st; S.sq = sq;
+  S.dpre = chain_buf(c, L.dpre); S.encdy = chain_buf(c, L.encdy);
+  S.ex = (size_t)c->B * c->Sx * c->d;
+  if (hoist) chain_rel_groups(c, L, true, S.RG);
+  chain_guided_set(c, true, hoist, S.GS);
+  S.G = -1;
+  for (int i = 0; i < c->n_ops && S.G < 0; ++i)
+    if (S.GS.hoisted[i]) S.G = i;
+  if (L.n_guided > S.GS.n && hipMemsetAsync(S.dpre, 0, S.ex * sizeof(float), st) != hipSuccess) return MMNAS_E_LAUNCH;
+  return MMNAS_OK;
+}
+// entering the encoder: its output gradient = the head's + the guided operators'
+static int chain_enc_dy(ChainBwd& S, hipStream_t s, const float** out) {
+  const mmnas_chain* c = S.c;
+  MMNAS_REQUIRE(c->dx_out || S.L->n_guided, MMNAS_E_ARG, "chain_bwd: no gradient reaches the encoder (dx_out NULL, no guided operator)");
+  if (S.enc_grad) { *out = S.enc_grad; return MMNAS_OK; }
+  if (c->dx_out && S.L->n_guided) {
+    const int r = mmnas_drop_add(c->dx_out, S.dpre, S.encdy, S.ex, 0.f, 0, 0, s);
+    if (r) return r;
+    *out = S.encdy;
+  } else *out = c->dx_out ? c->dx_out : S.dpre;
+  return MMNAS_OK;
+}
+// behind operator i's backward: when it is the last hoisted guided operator in backward order, every hoisted dK / dV exists
+static int chain_guided_release(ChainBwd& S, int i, hipStream_t s) {
+  if (!S.GS.n || i != S.G) return MMNAS_OK;
+  const int r = chain_guided_kv_bwd(S.c, *S.L, S.GS, S.c->dx_out, S.GS.n < S.L->n_guided ? S.dpre : nullptr, S.encdy, s);
+  if (!r) S.enc_grad = S.encdy;
+  return r;
+}
+// Behind the backward of operator / node i, issued on stream s.  A stream's first operator is its last in backward order: every
+// relation operator's bias gradient exists now -- before operator `mark`'s mark event (mark < 0: none), which covers the relation
+// parameters, see nets._chain.
+static int chain_first_done(ChainBwd& S, int i, int mark, hipStream_t s) {
+  const mmnas_chain* c = S.c; const ChainLayout& L = *S.L;
+  int r;
+  hipStream_t mark_stream = s;
+  if (i == L.first_y && !S.RG.groups[1].empty()) {
+    SideCtx* rsc = (rel_overlap_on() && L.last_x >= 0 && !S.sq) ? side_ctx(S.st, true) : nullptr;
+    if (rsc) {   // beside the encoder's backward (see rel_overlap_on); joined at the end of the call
+      if ((r = ev_fork(s, rsc->side, rsc->ovl[2]))) return r;
+      if ((r = chain_rel_bwd(S.RG, 1, rsc->side))) return r;
+      S.rel_bwd_side = rsc;
+      mark_stream = rsc->side;
+    } else if ((r = chain_rel_bwd(S.RG, 1, s))) return r;
+  }
+  if (i == L.first_x && !S.RG.groups[0].empty()) {
+    // (every relation group shares ONE partial-row workspace: the image stream's launches on the side stream are joined
+    //  before the language stream's write into it -- ADVICE r5; the join at the end of the call then finds nothing pending)
+    if (S.rel_bwd_side) { if ((r = ev_fork(S.rel_bwd_side->side, s, S.rel_bwd_side->ovl[3]))) return r; S.rel_bwd_side = nullptr; }
+    if ((r = chain_rel_bwd(S.RG, 0, s))) return r;
+  }
+  if (mark >= 0 && c->marks && c->marks[mark] && hipEventRecord((hipEvent_t)c->marks[mark], mark_stream) != hipSuccess) {
+    set_error("chain_bwd: cannot record the mark event of operator %d", mark);
+    return MMNAS_E_LAUNCH;
+  }
+  return MMNAS_OK;
+}
+// mixed chains: every node's pending gate-gradient reduction -- ONE launch at the end of the backward
+struct GateReds {
+  const float* part[MMNAS_CHAIN_MAX_OPS]; float* out[MMNAS_CHAIN_MAX_OPS]; int nwg[MMNAS_CHAIN_MAX_OPS], width[MMNAS_CHAIN_MAX_OPS];
+  int n = 0;
+};
+// chain exit: the last side-stream join, the gate gradients (reds: mixed chains), the input gradients of a stream without operators
+static int chain_bwd_close(ChainBwd& S, const GateReds* reds) {
+  const mmnas_chain* c = S.c; const ChainLayout& L = *S.L;
+  hipStream_t st = S.st;
+  int rc;
+  if (S.rel_bwd_side && (rc = ev_fork(S.rel_bwd_side->side, st, S.rel_bwd_side->ovl[3]))) return rc;   // the relation gradients are in
+  if (reds && reds->n && (rc = mixed_reduce_many(reds->part, reds->out, reds->nwg, reds->width, reds->n, st))) return rc;   // every node's gate gradients
+  if (L.first_y < 0 && hipMemcpyAsync(c->dy_in, c->dy_out, chain_rows_y(c) * c->d * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+    return MMNAS_E_LAUNCH;
+  if (L.first_x < 0) {
+    const float* g0 = c->dx_out;
+    if (S.enc_grad) g0 = S.enc_grad;
+    else if (c->dx_out && L.n_guided) {
+      if ((rc = mmnas_drop_add(c->dx_out, S.dpre, c->dx_in, S.ex, 0.f, 0, 0, st))) return rc;
+      g0 = nullptr;
+    } else if (!c->dx_out) g0 = S.dpre;
+    if (g0 && hipMemcpyAsync(c->dx_in, g0, S.ex * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return MMNAS_E_LAUNCH;
+  }
+  return MMNAS_OK;
+}
+
 // ---- mixed chains: the architecture step (MixedOp modes 'full' / 'two') ----
 // Per node: every evaluated candidate's forward up to its pre-LayerNorm sum, then ONE epilogue launch that normalises
 // all of them and forms the gated node output (mmnas_node_mix_fwd).  Backward: one launch turns the node's output
 // gradient into the gate gradients of all candidates (their outputs recomputed from the saved sums) and the sampled
 // candidate's output gradient; only that candidate's backward runs.
-struct NodeView { int first, n, active; const float* z[MMNAS_MIXED_MAX]; const float* a[MMNAS_MIXED_MAX]; const float* b[MMNAS_MIXED_MAX]; int cand[MMNAS_MIXED_MAX]; };
-
-// z / LayerNorm pointers of operator i (buffers from the arena): what the node epilogue reads for this candidate
-static void chain_cand_view(const mmnas_chain* c, const ChainLayout& L, int i, bool ln_done, const float** z, const float** la, const float** lb) {
-  char* base = (char*)c->arena;
-  const mmnas_chain_op& o = c->ops[i];
-  mmnas_att_op a; mmnas_mlp_op m;
-  chain_op_setup(c, i, a, m);
-  const bool norm = (o.kind == MMNAS_CHAIN_ATT ? a.flags : m.flags) & MMNAS_F_NORM;
-  if (!norm || ln_done) { *z = (const float*)(base + L.y[i]); *la = nullptr; *lb = nullptr; return; }
-  if (o.kind == MMNAS_CHAIN_ATT) {
-    a.save = base + L.save[i]; a.ws = nullptr;
-    *z = att_layout(&a).z; *la = a.ln_a; *lb = a.ln_b;
-  } else {
-    m.save = base + L.save[i]; m.ws = nullptr;
-    *z = mlp_layout(&m).z; *la = m.ln_a; *lb = m.ln_b;
-  }
-}
-
-// whether operator i's forward normalises its own output even when asked to defer (the one-launch short-sequence kernel)
-static bool chain_ln_done_in_op(const mmnas_chain* c, int i) {
-  const mmnas_chain_op& o = c->ops[i];
-  if (o.kind != MMNAS_CHAIN_ATT) return false;
-  mmnas_att_op a; mmnas_mlp_op m;
-  chain_op_setup(c, i, a, m);
-  return sa_small_applies(&a);
-}
-
 static int chain_fwd_mixed(const mmnas_chain* c, hipStream_t st, const ChainLayout& L) {
-  char* base = (char*)c->arena;
-  const float* cur_x = c->x_in;
-  const float* cur_y = c->y_in;
-  const size_t nx = (size_t)c->B * c->Sx * c->d * sizeof(float), ny = chain_rows_y(c) * c->d * sizeof(float);
   int rc;
   RelGroups RG;     // every relation candidate's bias (18 in the VQA search space) before the first node
   chain_rel_groups(c, L, false, RG);
-  SideCtx* rsc = (rel_overlap_on() && !RG.groups[1].empty() && L.last_x >= 0 && L.first_y >= 0) ? side_ctx(st, true) : nullptr;
-  if (rsc) {   // the image stream's candidates beside the encoder nodes (see rel_overlap_on); joined in front of the first decoder node
-    if ((rc = ev_fork(st, rsc->side, rsc->ovl[0]))) return rc;
-    if ((rc = chain_rel_fwd(RG, rsc->side, 1))) return rc;
-    if ((rc = chain_rel_fwd(RG, st, 0))) return rc;
-  } else if ((rc = chain_rel_fwd(RG, st))) return rc;
+  SideCtx* rsc = nullptr;   // the image stream's candidates beside the encoder nodes; joined in front of the first decoder node
+  if ((rc = chain_rel_prologue(c, L, RG, st, true, &rsc))) return rc;
   for (int i0 = 0; i0 < c->n_ops;) {
     int i1 = i0;
     while (i1 < c->n_ops && c->ops[i1].node == c->ops[i0].node) ++i1;
-    const bool oy = c->ops[i0].on_y;
-    if (rsc && i0 == L.first_y && (rc = ev_fork(rsc->side, st, rsc->ovl[1]))) return rc;   // every relation bias exists from here on
-    const float* cur = oy ? cur_y : cur_x;
-    const float* z[MMNAS_MIXED_MAX]; const float* la[MMNAS_MIXED_MAX]; const float* lb[MMNAS_MIXED_MAX];
-    float gate_order[MMNAS_MIXED_MAX];
-    (void)gate_order;
-    float eps = 1e-6f;
+    if (rsc && i0 == L.first_y && (rc = chain_rel_join(rsc, st))) return rc;
+    BoundOp cand[MMNAS_MIXED_MAX];   // the node's candidates: each writes its own block, the epilogue the node's output
+    for (int i = i0; i < i1; ++i) {
+      chain_bind(c, L, i, cand[i - i0], true);
+      chain_bind_fwd(cand[i - i0], c, L, cand[i - i0].y);
+    }
     // The node's attention candidates on the general path run stage by stage, each stage ONE launch for all of them: their
     // Q / K / V projections (up to 9 groups: same N = d_inside, K = d), their cores, their merge projections (own dropout
     // seed per group).  3 + 3 launches -> 1 + 1 per decoder node of the VQA search space (self / relation / guided).
-    mmnas_att_op ga[MMNAS_MIXED_MAX];
-    AttLayout gl[MMNAS_MIXED_MAX];
-    int gidx[MMNAS_MIXED_MAX], ng = 0;
+    const BoundOp* g[MMNAS_MIXED_MAX];
+    int ng = 0;
     for (int i = i0; i < i1; ++i) {
-      const mmnas_chain_op& o = c->ops[i];
-      if (o.kind != MMNAS_CHAIN_ATT) continue;
-      mmnas_att_op a; mmnas_mlp_op m;
-      chain_op_setup(c, i, a, m);
-      a.xq = cur;
-      a.xkv = (a.flags & MMNAS_F_SELF) ? cur : cur_x;
-      a.y = (float*)(base + L.y[i]); a.save = base + L.save[i]; a.ws = base + L.ws[i];
-      if (sa_small_applies(&a)) continue;
+      const BoundOp& b = cand[i - i0];
+      if (!b.att || att_ln_place(&b.a).fwd) continue;
       if (ng > 0) {
-        const mmnas_att_op& f = ga[0];
-        const bool d0 = (f.flags & MMNAS_F_TRAIN) && f.drop_p > 0.f, d1 = (a.flags & MMNAS_F_TRAIN) && a.drop_p > 0.f;
-        if (a.di != f.di || ((a.flags ^ f.flags) & MMNAS_F_RESIDUAL) || d0 != d1 || (d0 && a.drop_p != f.drop_p)) continue;
+        const mmnas_att_op& f = g[0]->a;
+        const bool d0 = drops(&f), d1 = drops(&b.a);
+        if (b.a.di != f.di || ((b.a.flags ^ f.flags) & MMNAS_F_RESIDUAL) || d0 != d1 || (d0 && b.a.drop_p != f.drop_p)) continue;
       }
       if (3 * (ng + 1) > MMNAS_GEMM_MAX_GROUPS) continue;
-      if ((rc = att_fwd_args(&a))) return rc;
-      ga[ng] = a; gl[ng] = att_layout(&a); gidx[ng] = i; ++ng;
+      if ((rc = att_fwd_args(&b.a))) return rc;
+      g[ng++] = &b;
     }
     if (ng < 2) ng = 0;   // (a single one takes the per-operator route below)
     if (ng) {
-      const mmnas_att_op& f = ga[0];
-      const bool drop = (f.flags & MMNAS_F_TRAIN) && f.drop_p > 0.f;
-      mmnas_gemm_desc g;
-      gemm_init(g, MMNAS_GEMM_NT, f.di, c->d, c->d, c->d, f.di);
-      g.ngroups = 3 * ng;
-      for (int j = 0; j < ng; ++j) att_qkv_groups(&ga[j], gl[j], g.g + 3 * j);
-      if ((rc = mmnas_gemm(&g, st))) return rc;
+      const mmnas_att_op& f = g[0]->a;
+      mmnas_gemm_desc gd;
+      gemm_init(gd, MMNAS_GEMM_NT, f.di, c->d, c->d, c->d, f.di);
+      gd.ngroups = 3 * ng;
+      for (int j = 0; j < ng; ++j) att_qkv_groups(&g[j]->a, g[j]->al, gd.g + 3 * j);
+      if ((rc = mmnas_gemm(&gd, st))) return rc;
       {   // the cores: two of one geometry (self / relation-self) share a launch, the rest one by one
         mmnas_mha_desc md[MMNAS_MIXED_MAX];
         for (int j = 0; j < ng; ++j)
-          if ((rc = att_core_fwd(&ga[j], gl[j], st, &md[j], RG.hoisted[gidx[j]]))) return rc;   // (relation biases first, unless hoisted)
+          if ((rc = att_core_fwd(&g[j]->a, g[j]->al, st, &md[j], RG.hoisted[g[j]->i]))) return rc;   // (relation biases first, unless hoisted)
         bool done[MMNAS_MIXED_MAX] = {false};
         for (int j = 0; j < ng; ++j) {
           if (done[j]) continue;
@@ -1111,214 +1279,106 @@ static int chain_fwd_mixed(const mmnas_chain* c, hipStream_t st, const ChainLayo
           done[j] = true;
         }
       }
-      gemm_init(g, MMNAS_GEMM_NT, c->d, f.di, f.di, f.di, c->d);
-      g.ngroups = ng;
-      for (int j = 0; j < ng; ++j) att_merge_group(&ga[j], gl[j], &g.g[j]);
-      if (f.flags & MMNAS_F_RESIDUAL) g.ldres = c->d;
-      if (drop) { g.drop_p = f.drop_p; g.drop_site = 1; g.drop_seed = f.seed; }
-      if ((rc = mmnas_gemm(&g, st))) return rc;
+      gemm_init(gd, MMNAS_GEMM_NT, c->d, f.di, f.di, f.di, c->d);
+      gd.ngroups = ng;
+      for (int j = 0; j < ng; ++j) att_merge_group(&g[j]->a, g[j]->al, &gd.g[j]);
+      if (f.flags & MMNAS_F_RESIDUAL) gd.ldres = c->d;
+      if (drops(&f)) { gd.drop_p = f.drop_p; gd.drop_site = 1; gd.drop_seed = f.seed; }
+      if ((rc = mmnas_gemm(&gd, st))) return rc;
     }
-    for (int i = i0; i < i1; ++i) {
-      const mmnas_chain_op& o = c->ops[i];
-      mmnas_att_op a; mmnas_mlp_op m;
-      chain_op_setup(c, i, a, m);
-      bool ln_done = true;
-      bool staged = false;
-      for (int j = 0; j < ng; ++j) staged |= gidx[j] == i;
-      if (staged) {   // (NORM: the node epilogue normalises; otherwise the merge product wrote the output)
-        ln_done = !(a.flags & MMNAS_F_NORM);
-        if (a.flags & MMNAS_F_NORM) eps = a.eps;
-        chain_cand_view(c, L, i, ln_done, &z[i - i0], &la[i - i0], &lb[i - i0]);
-        continue;
-      }
-      if (o.kind == MMNAS_CHAIN_ATT) {
-        a.xq = cur;
-        a.xkv = (a.flags & MMNAS_F_SELF) ? cur : cur_x;
-        a.y = (float*)(base + L.y[i]); a.save = base + L.save[i]; a.ws = base + L.ws[i];
-        if ((rc = att_fwd_impl(&a, st, true, &ln_done, RG.hoisted[i]))) return rc;
-        if (a.flags & MMNAS_F_NORM) eps = a.eps;
-      } else {
-        m.x = cur; m.y = (float*)(base + L.y[i]); m.save = base + L.save[i]; m.ws = base + L.ws[i];
-        if ((rc = mlp_fwd_impl(&m, st, true, &ln_done))) return rc;
-        if (m.flags & MMNAS_F_NORM) eps = m.eps;
-      }
-      chain_cand_view(c, L, i, ln_done, &z[i - i0], &la[i - i0], &lb[i - i0]);
-    }
-    // the gate values of the node's candidates, in operator order: a row of the [n_nodes, width] block picked apart
-    // by candidate index -- the kernel reads gate[j] for operator j, so the operators are passed in candidate order
+    // the remaining candidates one by one, and what the epilogue reads for each.  The gate values of the node's candidates are a
+    // row of the [n_nodes, width] block picked apart by candidate index -- the kernel reads gate[j] for entry j, so the
+    // candidates are passed in candidate order
+    // (candidates of the node that were not evaluated -- mode 'two' -- stay NULL: no term in the sum, no gate gradient)
     const float* zs[MMNAS_MIXED_MAX] = {nullptr}; const float* as[MMNAS_MIXED_MAX] = {nullptr}; const float* bs[MMNAS_MIXED_MAX] = {nullptr};
     int width = 0;
+    float eps = 1e-6f;
     for (int i = i0; i < i1; ++i) {
+      const BoundOp& b = cand[i - i0];
+      bool staged = false;
+      for (int j = 0; j < ng; ++j) staged |= g[j] == &b;
+      // (who normalised is not asked of the launch: att_fwd_impl and chain_cand_view take the same att_ln_place answer; a staged
+      //  candidate never normalises itself -- NORM: the node epilogue does; otherwise the merge product wrote the output)
+      bool ln_done;
+      if (!staged && (rc = chain_run_fwd(b, st, true, &ln_done, RG.hoisted[i], false))) return rc;
+      if (b.flags() & MMNAS_F_NORM) eps = b.eps();
       const int k = c->ops[i].cand;
-      zs[k] = z[i - i0]; as[k] = la[i - i0]; bs[k] = lb[i - i0];
+      chain_cand_view(b, &zs[k], &as[k], &bs[k]);
       if (k + 1 > width) width = k + 1;
     }
-    // (candidates of the node that were not evaluated -- mode 'two' -- stay NULL: no term in the sum, no gate gradient)
-    float* out = i0 == L.last_x ? c->x_out : (i0 == L.last_y ? c->y_out : (float*)(base + L.nout[i0]));
-    const int M = oy ? (int)chain_rows_y(c) : c->B * c->Sx;
-    if ((rc = mmnas_node_mix_fwd(zs, as, bs, width, c->gate + (size_t)c->ops[i0].node * c->gate_width, out, M, c->d, eps, st))) return rc;
-    if (oy) cur_y = out; else cur_x = out;
+    const int M = c->ops[i0].on_y ? (int)chain_rows_y(c) : c->B * c->Sx;
+    if ((rc = mmnas_node_mix_fwd(zs, as, bs, width, c->gate + (size_t)c->ops[i0].node * c->gate_width, chain_out(c, L, i0), M, c->d, eps, st))) return rc;
     i0 = i1;
   }
-  if (L.last_x < 0 && hipMemcpyAsync(c->x_out, c->x_in, nx, hipMemcpyDeviceToDevice, st) != hipSuccess) return MMNAS_E_LAUNCH;
-  if (L.last_y < 0 && hipMemcpyAsync(c->y_out, c->y_in, ny, hipMemcpyDeviceToDevice, st) != hipSuccess) return MMNAS_E_LAUNCH;
-  return MMNAS_OK;
+  return chain_fwd_passthrough(c, L, st);
 }
 
 static int chain_bwd_mixed(const mmnas_chain* c, hipStream_t st, const ChainLayout& L) {
   MMNAS_REQUIRE(c->dgate, MMNAS_E_ARG, "chain_bwd: mixed chain without a gate-gradient block");
-  char* base = (char*)c->arena;
-  const size_t ex = (size_t)c->B * c->Sx * c->d, ey = chain_rows_y(c) * c->d;
-  float* dpre = (float*)(base + L.dpre);
   int rc;
-  GuidedSet GS;     // the sampled guided candidates: dK / dV wait for the grouped launches behind the first of them
-  chain_guided_set(c, true, true, GS);
-  int Gm = -1;      // chain index of the first differentiated guided candidate (the last in backward order)
-  for (int i = 0; i < c->n_ops && Gm < 0; ++i)
-    if (GS.hoisted[i]) Gm = i;
-  const float* enc_grad = nullptr;
-  if (L.n_guided > GS.n && hipMemsetAsync(dpre, 0, ex * sizeof(float), st) != hipSuccess) return MMNAS_E_LAUNCH;
+  ChainBwd S;       // the sampled relation / guided candidates are the hoisted ones
+  if ((rc = chain_bwd_begin(S, c, L, st, nullptr, true))) return rc;
+  GateReds reds;
   // node starts in order
   int starts[MMNAS_CHAIN_MAX_OPS + 1], nn = 0;
   for (int i = 0; i < c->n_ops; ++i)
-    if (i == 0 || c->ops[i].node != c->ops[i - 1].node) starts[nn++] = i;
+    if (L.head[i] == i) starts[nn++] = i;
   starts[nn] = c->n_ops;
-  auto node_out = [&](int i0) -> const float* { return i0 == L.last_x ? c->x_out : (i0 == L.last_y ? c->y_out : (const float*)(base + L.nout[i0])); };
-  auto input_of = [&](int k) -> const float* {   // input of node k = output of the previous node on its stream
-    const bool oy = c->ops[starts[k]].on_y;
-    for (int j = k - 1; j >= 0; --j)
-      if ((bool)c->ops[starts[j]].on_y == oy) return node_out(starts[j]);
-    return oy ? c->y_in : c->x_in;
-  };
-  const float* x_final = L.last_x >= 0 ? c->x_out : c->x_in;
   const float* cur_dy = c->dy_out;
-  const float* red_part[MMNAS_CHAIN_MAX_OPS]; float* red_out[MMNAS_CHAIN_MAX_OPS]; int red_nwg[MMNAS_CHAIN_MAX_OPS], red_n[MMNAS_CHAIN_MAX_OPS];
-  int n_red = 0;
-  RelGroups RG;     // the sampled relation candidates: their bias gradients wait for one launch behind the stream's first node
-  chain_rel_groups(c, L, true, RG);
-  SideCtx* rel_bwd_side = nullptr;
   for (int k = nn - 1; k >= 0; --k) {
     const int i0 = starts[k], i1 = starts[k + 1];
-    const bool oy = c->ops[i0].on_y;
-    if (!oy && i0 == L.last_x) {   // entering the encoder: its output gradient = the head's + the guided operators'
-      MMNAS_REQUIRE(c->dx_out || L.n_guided, MMNAS_E_ARG, "chain_bwd: no gradient reaches the encoder (dx_out NULL, no guided operator)");
-      if (enc_grad) cur_dy = enc_grad;
-      else if (c->dx_out && L.n_guided) {
-        float* g0 = (float*)(base + L.encdy);
-        if ((rc = mmnas_drop_add(c->dx_out, dpre, g0, ex, 0.f, 0, 0, st))) return rc;
-        cur_dy = g0;
-      } else cur_dy = c->dx_out ? c->dx_out : dpre;
-    }
+    if (i0 == L.last_x && (rc = chain_enc_dy(S, st, &cur_dy))) return rc;
+    BoundOp cand[MMNAS_MIXED_MAX];
     const float* zs[MMNAS_MIXED_MAX] = {nullptr}; const float* as[MMNAS_MIXED_MAX] = {nullptr}; const float* bs[MMNAS_MIXED_MAX] = {nullptr};
     int width = 0, act = -1, act_op = -1;
+    LnPlace act_ln = {false, false};
     float eps = 1e-6f;
     for (int i = i0; i < i1; ++i) {
+      BoundOp& b = cand[i - i0];
+      chain_bind(c, L, i, b, true);
       const int kc = c->ops[i].cand;
-      chain_cand_view(c, L, i, chain_ln_done_in_op(c, i), &zs[kc], &as[kc], &bs[kc]);
+      const LnPlace p = chain_cand_view(b, &zs[kc], &as[kc], &bs[kc]);
       if (kc + 1 > width) width = kc + 1;
-      if (!c->ops[i].detached) { act = kc; act_op = i; }
-      const mmnas_chain_op& o = c->ops[i];
-      if (o.kind == MMNAS_CHAIN_ATT) { if (o.att.flags & MMNAS_F_NORM) eps = o.att.eps; }
-      else if (o.mlp.flags & MMNAS_F_NORM) eps = o.mlp.eps;
+      if (!c->ops[i].detached) { act = kc; act_op = i; act_ln = p; }
+      if (b.flags() & MMNAS_F_NORM) eps = b.eps();
     }
-    const float* nin = input_of(k);
-    float* dact = (float*)(base + L.ndact[i0]);
-    const int M = oy ? (int)chain_rows_y(c) : c->B * c->Sx;
+    float* dact = chain_node_dact(c, L, i0);
+    const int M = c->ops[i0].on_y ? (int)chain_rows_y(c) : c->B * c->Sx;
     const size_t grow = (size_t)c->ops[i0].node * c->gate_width;
-    // the sampled candidate: its descriptor first -- its LayerNorm backward rides in the node's mix kernel (round 6) unless the
-    // candidate takes the one-launch short-sequence backward, which does its own
-    const mmnas_chain_op& o = c->ops[act_op];
-    mmnas_att_op a; mmnas_mlp_op m;
-    chain_op_setup(c, act_op, a, m);
-    float* dx = i0 == L.first_x ? c->dx_in : (i0 == L.first_y ? c->dy_in : (float*)(base + L.dx[act_op]));
+    // The sampled candidate: its descriptor first -- its LayerNorm backward rides in the node's mix kernel (round 6) when the
+    // epilogue's view carries the candidate's LayerNorm parameters, i.e. its own forward did not normalise, and the candidate
+    // does not take the one-launch short-sequence backward, which does its own.  Otherwise the mix kernel hands on the
+    // gradient of the candidate's output and the candidate's backward starts at its LayerNorm.
+    BoundOp& b = cand[act_op - i0];
+    float* dx = chain_bind_bwd(b, c, L, dact);
     NodeLnBwd lnb;
     lnb.dz = nullptr;
     AuxReduce lnpre;
     lnpre.part = nullptr;
-    if (o.kind == MMNAS_CHAIN_ATT) {
-      const bool self = a.flags & MMNAS_F_SELF;
-      a.xq = nin;
-      a.xkv = self ? nin : x_final;
-      a.save = base + L.save[act_op]; a.ws = base + L.ws[act_op];
-      a.dy = dact; a.dxq = dx;
-      a.dxkv = self ? nullptr : dpre;
-      a.drel = nullptr;
-      if (node_lnb_on() && (a.flags & MMNAS_F_NORM) && c->d <= 256 && !(self && !(a.flags & MMNAS_F_REL) && sa_small_bwd_applies(&a))) {
-        const AttLayout AL = att_layout(&a);
-        const bool drop = (a.flags & MMNAS_F_TRAIN) && a.drop_p > 0.f;
-        lnb.dz = AL.dz; lnb.dt = drop ? AL.dt : nullptr; lnb.part = AL.lnws;
-        lnb.drop = make_drop(drop ? a.drop_p : 0.f, a.seed, 1);
-        lnpre.part = AL.lnws; lnpre.d = c->d;
-        lnpre.out[0] = a.dln_a; lnpre.out[1] = a.dln_b; lnpre.out[2] = nullptr;
-      }
-    } else {
-      m.x = nin; m.save = base + L.save[act_op]; m.ws = base + L.ws[act_op];
-      m.dy = dact; m.dx = dx;
-      if (node_lnb_on() && (m.flags & MMNAS_F_NORM) && c->d <= 256) {
-        const MlpLayout ML = mlp_layout(&m);
-        const bool drop = (m.flags & MMNAS_F_TRAIN) && m.drop_p > 0.f;
-        lnb.dz = ML.dz; lnb.dt = drop ? ML.dt : nullptr; lnb.part = ML.lnws;
-        lnb.drop = make_drop(drop ? m.drop_p : 0.f, m.seed, 1);
-        lnpre.part = ML.lnws; lnpre.d = c->d;
-        lnpre.out[0] = m.dln_a; lnpre.out[1] = m.dln_b; lnpre.out[2] = (drop && m.db[m.nl - 1]) ? m.db[m.nl - 1] : nullptr;
-      }
+    if (node_lnb_on() && c->d <= 256 && as[act] && !act_ln.bwd) {
+      const bool drop = b.att ? drops(&b.a) : drops(&b.m);
+      lnb.dz = b.att ? b.al.dz : b.ml.dz; lnb.dt = !drop ? nullptr : (b.att ? b.al.dt : b.ml.dt); lnb.part = b.att ? b.al.lnws : b.ml.lnws;
+      lnb.drop = make_drop(drop ? (b.att ? b.a.drop_p : b.m.drop_p) : 0.f, b.att ? b.a.seed : b.m.seed, 1);
+      lnpre.part = lnb.part; lnpre.d = c->d;
+      lnpre.out[0] = b.att ? b.a.dln_a : b.m.dln_a; lnpre.out[1] = b.att ? b.a.dln_b : b.m.dln_b;
+      lnpre.out[2] = (!b.att && drop && b.m.db[b.m.nl - 1]) ? b.m.db[b.m.nl - 1] : nullptr;   // (the last layer's bias gradient among the partial rows)
     }
     {
-      float* wsk = (float*)(base + L.mixws) + (size_t)k * mmnas_mixed_sum_ws_floats();
+      float* wsk = chain_gate_ws(c, L, k);
       int nwg = 0;
       if ((rc = node_mix_bwd_impl(zs, as, bs, width, c->gate + grow, cur_dy, dact, act, c->dgate + grow, wsk, M, c->d, eps, st, false, &nwg,
                                   lnb.dz ? &lnb : nullptr)))
         return rc;
-      if (nwg > 0) { red_part[n_red] = wsk; red_out[n_red] = c->dgate + grow; red_nwg[n_red] = nwg; red_n[n_red] = width; ++n_red; }
+      if (nwg > 0) { reds.part[reds.n] = wsk; reds.out[reds.n] = c->dgate + grow; reds.nwg[reds.n] = nwg; reds.width[reds.n] = width; ++reds.n; }
       lnpre.nrows = nwg;
     }
     // the sampled candidate's backward
-    if (o.kind == MMNAS_CHAIN_ATT) {
-      const bool self = a.flags & MMNAS_F_SELF;
-      if ((rc = att_bwd_impl(&a, st, nullptr, !self, RG.hoisted[act_op], GS.hoisted[act_op], lnb.dz ? &lnpre : nullptr))) return rc;
-      if (GS.n && act_op == Gm) {
-        float* g0 = (float*)(base + L.encdy);
-        if ((rc = chain_guided_kv_bwd(c, L, GS, x_final, c->dx_out, GS.n < L.n_guided ? dpre : nullptr, g0, st))) return rc;
-        enc_grad = g0;
-      }
-    } else {
-      if ((rc = mlp_bwd_impl(&m, st, nullptr, lnb.dz ? &lnpre : nullptr))) return rc;
-    }
+    if ((rc = chain_run_bwd(b, st, nullptr, S.RG.hoisted[act_op], S.GS.hoisted[act_op], lnb.dz ? &lnpre : nullptr))) return rc;
+    if ((rc = chain_guided_release(S, act_op, st))) return rc;
     cur_dy = dx;
-    hipStream_t mark_stream = st;
-    if (i0 == L.first_y && !RG.groups[1].empty()) {
-      SideCtx* rsc = (rel_overlap_on() && L.last_x >= 0) ? side_ctx(st, true) : nullptr;
-      if (rsc) {   // beside the encoder nodes' backward; joined at the end of the call
-        if ((rc = ev_fork(st, rsc->side, rsc->ovl[2]))) return rc;
-        if ((rc = chain_rel_bwd(RG, 1, rsc->side))) return rc;
-        rel_bwd_side = rsc;
-        mark_stream = rsc->side;
-      } else if ((rc = chain_rel_bwd(RG, 1, st))) return rc;
-    }
-    if (i0 == L.first_x && !RG.groups[0].empty()) {
-      // (every relation group shares ONE partial-row workspace: the image stream's launches on the side stream are joined
-      //  before the language stream's write into it -- ADVICE r5; the join at the end of the call then finds nothing pending)
-      if (rel_bwd_side) { if ((rc = ev_fork(rel_bwd_side->side, st, rel_bwd_side->ovl[3]))) return rc; rel_bwd_side = nullptr; }
-      if ((rc = chain_rel_bwd(RG, 0, st))) return rc;
-    }
-    if (c->marks && c->marks[act_op] && hipEventRecord((hipEvent_t)c->marks[act_op], mark_stream) != hipSuccess) {
-      set_error("chain_bwd: cannot record the mark event of operator %d", act_op);
-      return MMNAS_E_LAUNCH;
-    }
+    if ((rc = chain_first_done(S, i0, act_op, st))) return rc;
   }
-  if (rel_bwd_side && (rc = ev_fork(rel_bwd_side->side, st, rel_bwd_side->ovl[3]))) return rc;   // the relation gradients are in
-  if (n_red && (rc = mixed_reduce_many(red_part, red_out, red_nwg, red_n, n_red, st))) return rc;   // every node's gate gradients
-  if (L.first_y < 0 && hipMemcpyAsync(c->dy_in, c->dy_out, ey * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return MMNAS_E_LAUNCH;
-  if (L.first_x < 0) {
-    const float* g0 = c->dx_out;
-    if (enc_grad) g0 = enc_grad;
-    else if (c->dx_out && L.n_guided) {
-      if ((rc = mmnas_drop_add(c->dx_out, dpre, c->dx_in, ex, 0.f, 0, 0, st))) return rc;
-      g0 = nullptr;
-    } else if (!c->dx_out) g0 = dpre;
-    if (g0 && hipMemcpyAsync(c->dx_in, g0, ex * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return MMNAS_E_LAUNCH;
-  }
-  return MMNAS_OK;
+  return chain_bwd_close(S, &reds);
 }
 }  // namespace mmnas
 
@@ -1330,53 +1390,30 @@ extern "C" int mmnas_chain_fwd(const mmnas_chain* c, void* stream) {
   ChainLayout L;
   if ((rc = chain_layout(c, L))) return rc;
   if (c->mixed) return chain_fwd_mixed(c, st, L);
-  char* base = (char*)c->arena;
-  const float* cur_x = c->x_in;
-  const float* cur_y = c->y_in;
-  const size_t nx = (size_t)c->B * c->Sx * c->d * sizeof(float), ny = chain_rows_y(c) * c->d * sizeof(float);
   RelGroups RG;     // the relation bias of every relation operator of the chain: one launch per stream, here
   chain_rel_groups(c, L, false, RG);
   const int G = first_guided(c);
   const bool ovl = chain_overlap_on() && !c->use_side_stream && L.last_x >= 0 && L.first_y >= 0 && G > L.first_y;
   // the image stream's bias beside the encoder (see rel_overlap_on): joined in front of the decoder's first relation operator
-  int rel_join_at = -1;
   SideCtx* rsc = nullptr;
-  if (!ovl && rel_overlap_on() && !RG.groups[1].empty() && L.last_x >= 0 && (rsc = side_ctx(st, true)) != nullptr) {
-    for (int i = L.first_y; i < c->n_ops && rel_join_at < 0; ++i)
-      if (RG.hoisted[i] && c->ops[i].on_y) rel_join_at = i;
-  }
-  if (rel_join_at >= 0) {
-    if ((rc = ev_fork(st, rsc->side, rsc->ovl[0]))) return rc;
-    if ((rc = chain_rel_fwd(RG, rsc->side, 1))) return rc;
-    if ((rc = chain_rel_fwd(RG, st, 0))) return rc;
-  } else if ((rc = chain_rel_fwd(RG, st))) return rc;
+  if ((rc = chain_rel_prologue(c, L, RG, st, !ovl, &rsc))) return rc;
+  int rel_join_at = -1;
+  for (int i = L.first_y; rsc && i < c->n_ops && rel_join_at < 0; ++i)
+    if (RG.hoisted[i] && c->ops[i].on_y) rel_join_at = i;
   GuidedSet GS;
   chain_guided_set(c, false, !ovl, GS);
   auto run = [&](int i, hipStream_t s) -> int {
-    const mmnas_chain_op& o = c->ops[i];
-    mmnas_att_op a; mmnas_mlp_op m;
-    chain_op_setup(c, i, a, m);
-    const float* cur = o.on_y ? cur_y : cur_x;
-    float* out = i == L.last_x ? c->x_out : (i == L.last_y ? c->y_out : (float*)(base + L.y[i]));
-    int r;
-    if (o.kind == MMNAS_CHAIN_ATT) {
-      a.xq = cur;
-      a.xkv = (a.flags & MMNAS_F_SELF) ? cur : cur_x;   // guided: keys / values from the FINAL language state
-      a.y = out; a.save = base + L.save[i]; a.ws = base + L.ws[i];
-      bool done;
-      if ((r = att_fwd_impl(&a, s, false, &done, RG.hoisted[i], GS.hoisted[i]))) return r;
-    } else {
-      m.x = cur; m.y = out; m.save = base + L.save[i]; m.ws = base + L.ws[i];
-      if ((r = mmnas_mlp_op_fwd(&m, s))) return r;
-    }
-    if (o.on_y) cur_y = out; else cur_x = out;
-    return MMNAS_OK;
+    BoundOp b;
+    chain_bind(c, L, i, b);
+    chain_bind_fwd(b, c, L, chain_out(c, L, i));
+    bool done;
+    return chain_run_fwd(b, s, false, &done, RG.hoisted[i], GS.hoisted[i]);
   };
   if (!ovl) {
     for (int i = 0; i < c->n_ops; ++i) {
       // the final language state exists: key / value projections of every guided operator (grouped launches)
-      if (GS.n && i == G && (rc = chain_guided_kv_fwd(c, L, GS, cur_x, st))) return rc;
-      if (i == rel_join_at && (rc = ev_fork(rsc->side, st, rsc->ovl[1]))) return rc;   // the image stream's bias exists from here on
+      if (GS.n && i == G && (rc = chain_guided_kv_fwd(c, L, GS, st))) return rc;
+      if (i == rel_join_at && (rc = chain_rel_join(rsc, st))) return rc;
       if ((rc = run(i, st))) return rc;
     }
   } else {
@@ -1393,9 +1430,7 @@ extern "C" int mmnas_chain_fwd(const mmnas_chain* c, void* stream) {
     for (int i = G; i < c->n_ops; ++i)
       if ((rc = run(i, st))) return rc;
   }
-  if (L.last_x < 0 && hipMemcpyAsync(c->x_out, c->x_in, nx, hipMemcpyDeviceToDevice, st) != hipSuccess) return MMNAS_E_LAUNCH;
-  if (L.last_y < 0 && hipMemcpyAsync(c->y_out, c->y_in, ny, hipMemcpyDeviceToDevice, st) != hipSuccess) return MMNAS_E_LAUNCH;
-  return MMNAS_OK;
+  return chain_fwd_passthrough(c, L, st);
 }
 
 extern "C" int mmnas_chain_bwd(const mmnas_chain* c, void* stream) {
@@ -1419,95 +1454,28 @@ extern "C" int mmnas_chain_bwd(const mmnas_chain* c, void* stream) {
   // fills the latency-bound tail of the backward pass (encoder on 896 rows, LSTM, stem) instead.
   // (get(): the row records that it was read, so mmnas_switch_info reports it as it reports every cached switch)
   static const bool per_op = sw::side_flush.get() && !strcmp(getenv(sw::side_flush.name), "op");
-  char* base = (char*)c->arena;
-  const size_t ex = (size_t)c->B * c->Sx * c->d, ey = chain_rows_y(c) * c->d;
-  float* dpre = (float*)(base + L.dpre);
-  // inputs of operator i = outputs of the previous operator on its stream
-  auto input_of = [&](int i) -> const float* {
-    const bool oy = c->ops[i].on_y;
-    for (int j = i - 1; j >= 0; --j)
-      if ((bool)c->ops[j].on_y == oy) return j == L.last_x ? c->x_out : (j == L.last_y ? c->y_out : (const float*)(base + L.y[j]));
-    return oy ? c->y_in : c->x_in;
-  };
-  const float* x_final = L.last_x >= 0 ? c->x_out : c->x_in;
   const int G = first_guided(c);
   const bool ovl = chain_overlap_on() && !c->use_side_stream && L.last_x >= 0 && L.first_y >= 0 && G > L.first_y;
-  RelGroups RG;     // relation operators whose bias gradient waits for the one launch behind their stream's first operator
-  if (!ovl) chain_rel_groups(c, L, true, RG);
-  GuidedSet GS;     // guided operators whose dK / dV wait for the grouped launches behind operator G
-  chain_guided_set(c, true, !ovl, GS);
-  const float* enc_grad = nullptr;   // set by the hoisted launch: the encoder's output gradient, complete
-  SideCtx* rel_bwd_side = nullptr;   // set when the image stream's relation backward went to the side stream: joined below
-  if (L.n_guided > GS.n && hipMemsetAsync(dpre, 0, ex * sizeof(float), st) != hipSuccess) return MMNAS_E_LAUNCH;
+  ChainBwd S;
+  if ((rc = chain_bwd_begin(S, c, L, st, sq, !ovl))) return rc;
   // one operator's backward on stream s: gradient of its output in, gradient of its input out (returned through *dxo)
   auto run = [&](int i, hipStream_t s, const float* dyi, const float** dxo) -> int {
-    const mmnas_chain_op& o = c->ops[i];
-    mmnas_att_op a; mmnas_mlp_op m;
-    chain_op_setup(c, i, a, m);
-    float* dx = i == L.first_x ? c->dx_in : (i == L.first_y ? c->dy_in : (float*)(base + L.dx[i]));
+    BoundOp b;
+    chain_bind(c, L, i, b);
+    float* dx = chain_bind_bwd(b, c, L, dyi);
     int r;
-    if (o.kind == MMNAS_CHAIN_ATT) {
-      const bool self = a.flags & MMNAS_F_SELF;
-      a.xq = input_of(i);
-      a.xkv = self ? a.xq : x_final;
-      a.save = base + L.save[i]; a.ws = base + L.ws[i];
-      a.dy = dyi; a.dxq = dx;
-      a.dxkv = self ? nullptr : dpre;     // guided: added into the running sum (zeroed above)
-      a.drel = nullptr;
-      if ((r = att_bwd_impl(&a, s, sq, !self, RG.hoisted[i], GS.hoisted[i]))) return r;
-      if (GS.n && i == G) {   // the last guided operator in backward order: every hoisted dK / dV exists
-        float* g0 = (float*)(base + L.encdy);
-        if ((r = chain_guided_kv_bwd(c, L, GS, x_final, c->dx_out, GS.n < L.n_guided ? dpre : nullptr, g0, s))) return r;
-        enc_grad = g0;
-      }
-    } else {
-      m.x = input_of(i); m.save = base + L.save[i]; m.ws = base + L.ws[i];
-      m.dy = dyi; m.dx = dx;
-      if ((r = mlp_bwd_impl(&m, s, sq))) return r;
-    }
+    if ((r = chain_run_bwd(b, s, sq, S.RG.hoisted[i], S.GS.hoisted[i]))) return r;
+    if ((r = chain_guided_release(S, i, s))) return r;
     *dxo = dx;
-    // (the stream's first operator is its last in backward order: every relation operator's bias gradient exists now --
-    //  before this operator's mark, which covers the relation parameters, see nets._chain)
-    hipStream_t mark_stream = s;
-    if (i == L.first_y && !RG.groups[1].empty()) {
-      SideCtx* rsc = (rel_overlap_on() && L.last_x >= 0 && !sq) ? side_ctx(st, true) : nullptr;
-      if (rsc) {   // beside the encoder's backward (see rel_overlap_on); joined at the end of the call
-        if ((r = ev_fork(s, rsc->side, rsc->ovl[2]))) return r;
-        if ((r = chain_rel_bwd(RG, 1, rsc->side))) return r;
-        rel_bwd_side = rsc;
-        mark_stream = rsc->side;
-      } else if ((r = chain_rel_bwd(RG, 1, s))) return r;
-    }
-    if (i == L.first_x && !RG.groups[0].empty()) {
-      // (shared partial-row workspace: join the image stream's relation backward first, see chain_bwd_mixed)
-      if (rel_bwd_side) { if ((r = ev_fork(rel_bwd_side->side, s, rel_bwd_side->ovl[3]))) return r; rel_bwd_side = nullptr; }
-      if ((r = chain_rel_bwd(RG, 0, s))) return r;
-    }
     // (encoder / decoder overlap: an event behind operator i on ONE of the two streams says nothing about the operators
     //  with larger indices still running on the other -- the marks are recorded behind the join below instead)
-    if (!ovl && c->marks && c->marks[i] && hipEventRecord((hipEvent_t)c->marks[i], mark_stream) != hipSuccess) {
-      set_error("chain_bwd: cannot record the mark event of operator %d", i);
-      return MMNAS_E_LAUNCH;
-    }
-    return MMNAS_OK;
-  };
-  // entering the encoder: its output gradient = head's + the guided operators'
-  auto encoder_dy = [&](hipStream_t s, const float** out) -> int {
-    MMNAS_REQUIRE(c->dx_out || L.n_guided, MMNAS_E_ARG, "chain_bwd: no gradient reaches the encoder (dx_out NULL, no guided operator)");
-    if (enc_grad) { *out = enc_grad; return MMNAS_OK; }
-    if (c->dx_out && L.n_guided) {
-      float* g0 = (float*)(base + L.encdy);
-      const int r = mmnas_drop_add(c->dx_out, dpre, g0, ex, 0.f, 0, 0, s);
-      if (r) return r;
-      *out = g0;
-    } else *out = c->dx_out ? c->dx_out : dpre;
-    return MMNAS_OK;
+    return chain_first_done(S, i, ovl ? -1 : i, s);
   };
   const float* cur_dy = c->dy_out;
   if (!ovl) {
     for (int i = c->n_ops - 1; i >= 0; --i) {
       if (sq && i == L.last_x && (rc = q.flush(st, side, sc->ev[0]))) return rc;   // the decoder's parameter-gradient work
-      if (!c->ops[i].on_y && i == L.last_x && (rc = encoder_dy(st, &cur_dy))) return rc;
+      if (i == L.last_x && (rc = chain_enc_dy(S, st, &cur_dy))) return rc;
       if ((rc = run(i, st, cur_dy, &cur_dy))) return rc;
       if (sq && per_op && (rc = q.flush(st, side, sc->ev[i + 1]))) return rc;
     }
@@ -1519,7 +1487,7 @@ extern "C" int mmnas_chain_bwd(const mmnas_chain* c, void* stream) {
       if ((rc = run(i, st, cur_dy, &cur_dy))) return rc;
     if ((rc = ev_fork(st, oc->enc, oc->ovl[2]))) return rc;
     const float* enc_dy = nullptr;
-    if ((rc = encoder_dy(oc->enc, &enc_dy))) return rc;
+    if ((rc = chain_enc_dy(S, oc->enc, &enc_dy))) return rc;
     int ie = L.last_x, id = G - 1;
     while (ie >= L.first_x || id >= L.first_y) {    // encoder on its stream beside the decoder's leading operators
       if (ie >= L.first_x && (rc = run(ie--, oc->enc, enc_dy, &enc_dy))) return rc;
@@ -1533,18 +1501,7 @@ extern "C" int mmnas_chain_bwd(const mmnas_chain* c, void* stream) {
           return MMNAS_E_LAUNCH;
         }
   }
-  if (rel_bwd_side && (rc = ev_fork(rel_bwd_side->side, st, rel_bwd_side->ovl[3]))) return rc;   // the relation gradients are in
-  if (L.first_y < 0 && hipMemcpyAsync(c->dy_in, c->dy_out, ey * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return MMNAS_E_LAUNCH;
-  if (L.first_x < 0) {
-    const float* g0 = c->dx_out;
-    if (enc_grad) g0 = enc_grad;
-    else if (c->dx_out && L.n_guided) {
-      if ((rc = mmnas_drop_add(c->dx_out, dpre, c->dx_in, ex, 0.f, 0, 0, stream))) return rc;
-      g0 = nullptr;
-    } else if (!c->dx_out) g0 = dpre;
-    if (g0 && hipMemcpyAsync(c->dx_in, g0, ex * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return MMNAS_E_LAUNCH;
-  }
-  return MMNAS_OK;
+  return chain_bwd_close(S, nullptr);
 }
 
 extern "C" int mmnas_chain_join(void* main_stream, void* waiting_stream) {
@@ -1628,7 +1585,7 @@ extern "C" int mmnas_head_fwd(const mmnas_head* hd, void* stream) {
   if (rc) return rc;
   MMNAS_REQUIRE(hd->arena && hd->logits && hd->ln_a && hd->ln_b && hd->Wp, MMNAS_E_ARG, "head_fwd: null pointer");
   HeadLayout L = head_layout(hd);
-  const bool drop = (hd->flags & MMNAS_F_TRAIN) && hd->drop_p > 0.f;
+  const bool drop = drops(hd);
   const int B = hd->B, d = hd->d, MID = hd->MID, G = hd->G, OUT = hd->OUT;
   mmnas_gemm_desc g;
   hipStream_t st = (hipStream_t)stream;
@@ -1704,7 +1661,7 @@ extern "C" int mmnas_head_bwd(const mmnas_head* hd, void* stream) {
   if (rc) return rc;
   MMNAS_REQUIRE(hd->arena && hd->dlogits && hd->ln_a && hd->dln_a && hd->dln_b && hd->Wp && hd->dWp, MMNAS_E_ARG, "head_bwd: null pointer");
   HeadLayout L = head_layout(hd);
-  const bool drop = (hd->flags & MMNAS_F_TRAIN) && hd->drop_p > 0.f;
+  const bool drop = drops(hd);
   const float gate_scale = drop ? 1.0f / (1.0f - hd->drop_p) : 1.0f;
   const int B = hd->B, d = hd->d, MID = hd->MID, G = hd->G, OUT = hd->OUT, ANS = hd->ANS;
   hipStream_t st = (hipStream_t)stream;

@@ -42,6 +42,9 @@ _WEIGHT = [('vqa', 1, 3, 6, 9, 0.1), ('vqa', 2, 3, 6, 9, 0.1)]
 # MMNAS_MHA_PAIR is consulted by the mixed chain's forward only, and decides something only where two attention candidates of a
 # node share a geometry with more than 64 queries and 65..128 keys: an architecture step ('full': every candidate) at 100 regions
 _ARCH_PAIR = [(4242, 128, 2, 5, 100, 'full', 0.1)]
+# HSIZE 256: the smallest width the short-sequence kernels take (sa_small_applies: d in {256, 512}, <= 16 rows, heads of 64);
+# _ARCH_SMALL's 128 never reaches them
+_ARCH_SHORT = [(4242, 256, 3, 5, 7, 'full', 0.1), (4242, 256, 3, 5, 7, 'two', 0.1)]
 
 CASES = {
     'mha_fp32_mid': dict(env={'MMNAS_MHA_FWD_B16': '0', 'MMNAS_MHA_BWD_B16': '0'}, kind='mha', shapes=_MHA_MID),
@@ -58,13 +61,16 @@ CASES = {
     'rel_multi_yield3': dict(env={'MMNAS_REL_MULTI_YIELD': '3'}, kind='rel_multi', shapes=_REL_MULTI),
     'rel_multi_wgs1': dict(env={'MMNAS_REL_MULTI_WGS': '1'}, kind='rel_multi', shapes=_REL_MULTI),
     'chain_node_lnb0': dict(env={'MMNAS_NODE_LNB': '0'}, kind='arch', shapes=_ARCH_SMALL + _ARCH_WIDE),
+    # a sampled language-stream SelfAtt through the one-launch forward and then the GENERAL backward, inside the mixed chain
+    'chain_small_bwd0': dict(env={'MMNAS_SMALL_BWD': '0'}, kind='arch', shapes=_ARCH_SHORT),
     'chain_misc': dict(env={'MMNAS_MHA_PAIR': '0', 'MMNAS_HEAD_OVERLAP': '1', 'MMNAS_SIDE_FLUSH': 'op', 'MMNAS_SIDE_PRIO': '0'},
                        kind='chain_misc', shapes=_WEIGHT + _ARCH_PAIR),
 }
 
 # The kernels each case reaches that the default setting does not, read from the dispatch code (launch_fwd / launch_bwd,
 # mmnas_mha_core_fwd / _bwd and mha_core_fwd_pair in attention.hip; mha_fwd_b16_launch in attention_bwd16.hip; rf_bwd_impl in
-# relfused.hip; mmnas_rel_multi_fwd / _bwd in relmulti.hip; chain_bwd_mixed, mmnas_chain_bwd, side_ctx and the head in ops.hip).
+# relfused.hip; mmnas_rel_multi_fwd / _bwd in relmulti.hip; att_ln_place, chain_cand_view, chain_bwd_mixed, mmnas_chain_bwd, side_ctx and the head
+# in ops.hip).
 REACHES = {
     'mha_fp32_mid': 'mha_fwd_kernel<64,4,1> (1 query), <64,4,2> (33, 36 queries), <64,4,4> (97, 100, 128 queries; packed rows); '
                     'mha_bwd_fused_kernel<4,true|false> (dense and packed rows)',
@@ -80,6 +86,9 @@ REACHES = {
     'rel_multi_wgs1': 'the default instantiations on the grid of one workgroup per CU (forward)',
     'chain_node_lnb0': "node_mix_bwd without its LayerNorm part, then the candidate's LayerNorm backward as its own launch inside "
                        'att_bwd_impl / mlp_bwd_impl; at HSIZE 512 that is the route with the switch on or off',
+    'chain_small_bwd0': "sa_small_fwd for the sampled encoder SelfAtt (it normalises its own output: the node epilogue gets no LayerNorm for "
+                        "it), then node_mix_bwd without a LayerNorm part for that node and att_bwd_impl's general path from its own "
+                        'LayerNorm backward on (att_ln_place: forward yes, backward no)',
     'chain_misc': 'two mha_fwd_b16_kernel launches where the pair launch would run (arch step); the head with its two AttFlat sides '
                   'on two streams; side-stream parameter-gradient work flushed behind every operator; stream pairs without priorities',
 }
@@ -433,6 +442,8 @@ def run_arch(shape):
     c['cfg'].DROPOUT_R = dropout
     pl = cases.search_plan(np.random.RandomState(6), mode)
     plan = pl['enc'] + pl['dec']
+    if os.environ.get('MMNAS_SMALL_BWD') == '0':      # the switch decides something only for a sampled SelfAtt (candidate 0) of an encoder node
+        assert hsize in (256, 512) and Sx <= 16 and any(act == [0] for act, _ in pl['enc']), (shape, pl['enc'])
     inp = tuple(torch.from_numpy(a).to('cuda:0') for a in c['inputs'])
     tgt = torch.from_numpy(c['target']).to('cuda:0')
     res = {}

@@ -71,6 +71,11 @@ def test_host_only_entry_points_of_the_product_library():
     from tests import host_plan_driver
     out = host_plan_driver.run()
     assert out['mixed_chain_bytes'] > out['chain_bytes'] > 0 and out['head_bytes'] > 0
+    # the arena layouts are part of the contract (a backward call reads back what the forward call saved): the planners'
+    # byte counts for the driver's descriptors, as first recorded
+    assert {k: out[k] for k in ('chain_bytes', 'mixed_chain_bytes', 'head_bytes', 'att_save', 'att_ws', 'mlp_save')} == dict(
+        chain_bytes=1749299200, mixed_chain_bytes=6896418816, head_bytes=44863232, att_save=86425600, att_ws=102473728,
+        mlp_save=65536000)
 
 
 def test_product_path_refuses_cpu_tensors():
