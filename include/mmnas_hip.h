@@ -129,6 +129,14 @@ typedef struct mmnas_gemm_desc {
   uint32_t drop_site;
   uint64_t drop_seed;
   mmnas_gemm_group g[MMNAS_GEMM_MAX_GROUPS];
+  const int* ktab;        /* layout TN, accumulate: NULL (a zero-initialised descriptor) = the reduction walks K-tile q at row
+                             32 q.  Otherwise a device table of 1 + ceil(K / 32) int32, ktab[0] = count, ktab[1 .. count] =
+                             ascending start rows of disjoint 32-row K-tiles: only those tiles are reduced (rows behind K
+                             read as zero), the count tiles re-dealt evenly over the split-K pieces on the device.  The
+                             caller guarantees that every A row outside the tiles is exactly +-0.  A kernel variant
+                             without table support walks densely, which gives the same sums.
+                             (Appended to the descriptor: a caller compiled against the header without it must be rebuilt --
+                             its shorter struct leaves this field to whatever follows it.  Zero-initialise descriptors.) */
 } mmnas_gemm_desc;
 
 int mmnas_gemm(const mmnas_gemm_desc* d, void* stream);
@@ -671,6 +679,19 @@ int mmnas_chain_join(void* main_stream, void* waiting_stream);
  * last launch.  Measured: no gain on MI355X, so off by default (env MMNAS_CHAIN_OVERLAP=1 or this
  * call enable it; returns the previous setting).  Results are identical either way. */
 int mmnas_set_chain_overlap(int on);
+/* Live-row weight gradients (plain and mixed chains with y_mask, not the ragged stream; MMNAS_WGRAD_LIVE, default on; returns
+ * the previous setting).  Padded image rows are masked as keys in every attention and in AttFlat, so dy_out is exactly 0 on
+ * them, and every chain operator keeps a zero gradient row at exactly 0 (row-wise MLP / LayerNorm; dO = 0 gives dQ = 0, a
+ * masked key P = 0, hence dK = dV = 0): the image stream's dW += dY^T X products lose only addends that are exactly +-0.
+ * Precondition: a sample WITHOUT any unmasked key (its softmax over all-masked keys is uniform, not 0) has dy_out = +-0 on all
+ * of its rows or on none; the reference's heads give all-zero, a caller that cannot promise it switches the walk off. */
+int mmnas_set_wgrad_live(int on);
+/* The table those products walk (mmnas_gemm_desc::ktab), built by mmnas_chain_bwd from that call's dy_out: row r of
+ * dy [M, d] is dead iff mask[r] != 0 and all d values are +-0 (NaN / Inf: live); tab[0] = count, tab[1 .. count] = start rows
+ * of the greedy cover of the live rows by disjoint 32-row tiles (each starts on a live row; the last may pass M).  tab holds
+ * mmnas_wgrad_live_table_ints(M) int32 (table + scratch); M <= 8192, d % 4 == 0, dy 16-byte aligned. */
+int mmnas_wgrad_live_table_ints(int M);   /* host only */
+int mmnas_wgrad_live_table(const float* dy, const unsigned char* mask, int M, int d, int* tab, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Answer head: AttFlat over the language state + AttFlat over the image state, their sum, LayerNorm and the answer

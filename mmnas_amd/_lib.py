@@ -58,7 +58,7 @@ class GemmDesc(C.Structure):
                 ('lda', C.c_int), ('ldb', C.c_int), ('ldc', C.c_int), ('ldres', C.c_int), ('ldgate', C.c_int),
                 ('relu', C.c_int), ('split_k', C.c_int), ('accumulate', C.c_int), ('b_planes', C.c_int), ('alpha', C.c_float), ('gate_scale', C.c_float),
                 ('drop_p', C.c_float), ('drop_site', C.c_uint32), ('drop_seed', C.c_uint64),
-                ('g', GemmGroup * GEMM_MAX_GROUPS)]
+                ('g', GemmGroup * GEMM_MAX_GROUPS), ('ktab', _fp)]
 
 
 class MhaDesc(C.Structure):
@@ -216,6 +216,9 @@ SYMBOLS = {
     'mmnas_rel_multi_bwd': (_i, [C.POINTER(RelMulti), _fp]),
     'mmnas_set_rel_hoist': (_i, [_i]),
     'mmnas_set_rel_keylimit': (_i, [_i]),
+    'mmnas_set_wgrad_live': (_i, [_i]),
+    'mmnas_wgrad_live_table_ints': (_i, [_i]),
+    'mmnas_wgrad_live_table': (_i, [_fp, _fp, _i, _i, _fp, _fp]),
     'mmnas_set_guided_hoist': (_i, [_i]),
     'mmnas_set_rel_overlap': (_i, [_i]),
     'mmnas_mha_core_fwd': (_i, [C.POINTER(MhaDesc), _fp]),

@@ -27,6 +27,9 @@
 //     contributors in contributor order (bitwise reproducible, no float atomics, nobody waits) and
 //     runs the epilogue.  Weight gradients (TN, reduction over the 6400 rows) use the same mechanism
 //     instead of split-K atomics.
+//   * weight gradients of a padded batch (mmnas_gemm_desc::ktab, the lean split-K TN kernel): the reduction walks a device
+//     table of 32-row K-tiles that cover the live gradient rows instead of all of them; the grid is the dense one, the table's
+//     tiles are dealt evenly over its pieces on the device, so every piece has fewer K-tile rounds.
 //   * workgroup -> unit-range mapping is XCD-aware: the 8 XCDs (private 4 MiB L2 each) get contiguous
 //     runs of units, so an XCD re-reads only its own A row-panels and the (small) weight matrix.
 #include <stddef.h>
@@ -92,7 +95,13 @@ struct GemmK {
   float* lg_h2;
   float* lg_dc;
   const float* lg_act;
-  int lg_ldh2, lg_pad;
+  int lg_ldh2;
+  // live-row K-tile table of a weight gradient (mmnas_gemm_desc::ktab; LEAN TN kernels only, NULL: the dense walk).  The host
+  // fixes the grid -- ksl slices per output tile -- from T; the kernel deals the table's count tiles over them again:
+  // ceil(count / ksl) = ((count + ksl - 1) * ksl_magic) >> 32 K-tiles per piece, ksl_magic = ceil(2^32 / ksl)
+  int ksl;
+  unsigned ksl_magic;
+  const int* ktab;
   // (the groups last: the first three end inside the 512 bytes the warm-up loads touch)
   GemmGroupK g[MAXG];
 };
@@ -227,10 +236,14 @@ __device__ __forceinline__ void gemm_body(const GemmK& p, const int bid, const i
   static_assert(PF == 1 || (PF == 2 && FAST && (NS == 0 || NS == 1 || NS == 3)), "the two-stage prefetch exists for the buffer-load path (fp32, bf16x1 and bf16x6)");
   static_assert(NS == 0 || (FAST && BK == 32), "the bf16-split path exists for the buffer-load path only");
   static_assert(!BDMA || (NS == 3 && AKC && BKC && FAST && PF == 1 && BM == 64 && BN == 64 && EPI == 0), "LDS-DMA weight planes: NT 64^2 bf16x6 only");
+  static_assert(LEAN >= 0 && LEAN <= 4 && (LEAN != 4 || !AKC), "lean levels 1-3; 4 = TN with the live-row table");
   static_assert(!LEAN || (NS > 0 && (AKC || !BKC) && FAST && PF == 2 && BM == 64 && BN == 64 && EPI == 0 && !BDMA), "lean form: 64^2 split-operand kernels");
   // LEAN, TN (weight gradients): split-K pieces only ("C +=" by float atomics), one K-segment; the adds are buffer atomics
   // on one per-lane offset (range check = predication) instead of 16 guarded 64-bit address computations
   constexpr bool LEAN_TN = LEAN && !AKC;
+  // LEAN 4 (TN): the same with the live-row K-tile table (GemmK::ktab) -- an instantiation of its own, so that the dense walk's
+  // set-up and K loop stay exactly what they were (one more select per K-tile round measured +0.5 us per dense launch)
+  constexpr bool KTAB = LEAN == 4;
   // LEAN 3 (NN, whole tiles): the accumulators keep their natural layout (lane = column) and the epilogue works element by
   // element through buffer loads / stores on one per-lane offset -- for the products whose epilogue takes column sums (the
   // hidden-layer gradient of an FFN with its bias gradient): a column's rows sit in one lane's registers
@@ -295,6 +308,18 @@ __device__ __forceinline__ void gemm_body(const GemmK& p, const int bid, const i
   static_assert(MAXG == 9, "the list of group boundaries below names nine groups");
   asm volatile("" : "+s"(h.U), "+s"(h.gt[1]), "+s"(h.gt[2]), "+s"(h.gt[3]), "+s"(h.gt[4]), "+s"(h.gt[5]), "+s"(h.gt[6]), "+s"(h.gt[7]),
                "+s"(h.gt[8]));
+  // Live-row table (weight gradients of a padded batch): the count and the first 256 start rows, lane l of every wave holding
+  // entries l, l + 64, l + 128, l + 192 -- one batch of loads issued here, behind the header's, and first read behind the
+  // tile / offset set-up below, so its round trip hides under that set-up.  Entries behind the table's end (1 + T words) lie
+  // outside the buffer range and read as zero.
+  const int* const ktab = KTAB ? p.ktab : nullptr;
+  unsigned ktab_cnt = 0, ktab_w[4] = {0, 0, 0, 0};
+  if (KTAB) {
+    const __amdgpu_buffer_rsrc_t t_rs = __builtin_amdgcn_make_buffer_rsrc((void*)ktab, 0, (unsigned)(h.T + 1) * 4u, 0x00020000);
+    ktab_cnt = __builtin_amdgcn_raw_buffer_load_b32(t_rs, 0u, 0, 0);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ktab_w[j] = __builtin_amdgcn_raw_buffer_load_b32(t_rs, (unsigned)(1 + lane + 64 * j) * 4u, 0, 0);
+  }
   int v;
   {
     const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, in = bid >> 3;
@@ -316,6 +341,8 @@ __device__ __forceinline__ void gemm_body(const GemmK& p, const int bid, const i
 
   while (u < uend) {
     int tile, q0, nq;
+    int ksl_i = 0;   // (live-row table) this piece's slice: its K-tiles are dealt out behind the set-up
+    static_assert(!KTAB || LEAN_TN, "the table walk deals K-tiles over split-K slices: KTAB kernels are LEAN_TN, whose mode is MODE_SPLIT by construction");
     if (mode == MODE_TILE || whole >= 0) {
       tile = whole >= 0 ? whole : v; q0 = 0; nq = h.T;
       u = uend;
@@ -324,8 +351,9 @@ __device__ __forceinline__ void gemm_body(const GemmK& p, const int bid, const i
       tile = v - sl * h.ntiles;
       q0 = sl * h.P;
       nq = min(h.P, h.T - q0);
+      ksl_i = sl;
       u = uend;
-      if (nq <= 0) break;
+      if (nq <= 0 && !KTAB) break;
     } else {
       const int tt = u / h.T;  // tile among the streamed (tail) tiles
       tile = h.n_full + tt;
@@ -432,6 +460,23 @@ __device__ __forceinline__ void gemm_body(const GemmK& p, const int bid, const i
       bytesb = (unsigned)(BKC ? h.N : h.K) * (unsigned)h.ldb * 4u;
     }
 
+    // Live-row table: the piece covers table entries [q0, q0 + nq) of the count live tiles, dealt evenly over the ksl slices
+    // the grid was sized for (a slice with nothing left ends here: no operand load, no atomic add; count = 0 ends them all);
+    // lane t keeps the start row of the piece's K-tile t (at most 64 per piece, host check) for the readlane in gload_to.
+    int krow = 0;
+    if (KTAB) {
+      const int count = min(__builtin_amdgcn_readfirstlane((int)ktab_cnt), h.T);
+      const int pp = (int)__umulhi((unsigned)(count + p.ksl - 1), p.ksl_magic);
+      q0 = ksl_i * pp;
+      nq = min(pp, count - q0);
+      if (nq <= 0) break;
+      const int e = q0 + lane;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int vj = __shfl((int)ktab_w[j], e & 63, 64);
+        krow = (e >> 6) == j ? vj : krow;
+      }
+    }
     // unit q of the tile: segment q / ntk, K-tile q % ntk; `live` false (FAST path only): every offset is put out of
     // range, the buffer bounds check answers with zeros and no memory request is made -- a branch-free "no load"
     int seg_c = 0, kt_c = 0;   // segment / K-tile of the next unit gload_to is asked for
@@ -449,7 +494,12 @@ __device__ __forceinline__ void gemm_body(const GemmK& p, const int bid, const i
       if (FAST) {
         const __amdgpu_buffer_rsrc_t ra_src = __builtin_amdgcn_make_buffer_rsrc((void*)Ap, 0, bytesa, 0x00020000);
         const __amdgpu_buffer_rsrc_t rb_src = __builtin_amdgcn_make_buffer_rsrc((void*)Bp, 0, bytesb, 0x00020000);
-        const unsigned ka = (unsigned)kt * stepa, kb = (unsigned)kt * stepb;
+        unsigned ka = (unsigned)kt * stepa, kb = (unsigned)kt * stepb;
+        if (KTAB) {   // K-tile kt of the piece starts at the table's row: one readlane, no branch, no load
+          const unsigned row = (unsigned)__builtin_amdgcn_readlane(krow, (kt - q0) & 63);
+          ka = row * ((unsigned)h.lda * 4u);
+          kb = row * ((unsigned)h.ldb * 4u);
+        }
         if (LEAN_SW || LEAN_EL) {
           // (NT / NN; measured neutral to negative on the transposing loads of TN)  the K-tile's byte offset rides in the instruction's scalar offset -- the range check covers voffset + soffset and
           // a voffset of ~0u stays out of range (tools/probe/soffset_probe.hip) -- and "no load" is a descriptor of zero
@@ -1426,6 +1476,18 @@ static int plan_gemm(const mmnas_gemm_desc* d, hipStream_t st, GemmPlan& out) {
     }
     out.lean = ok ? 1 : 0;
     if (ok) k.nt_magic = (unsigned)(((1ull << 32) + (unsigned)k.ntiles - 1) / (unsigned)k.ntiles);
+    // live-row table: pieces of at most 64 K-tiles (one start row per lane) out of at most 256 (four table words per lane),
+    // at least two slices (ksl_magic = ceil(2^32 / S) does not fit 32 bits for S = 1; MODE_SPLIT has S >= 2 today);
+    // a tile that starts on the operand's last row ends 31 rows behind it -- still a 32-bit byte offset
+    const int S = nwg / k.ntiles;
+    if (ok && d->ktab && k.P <= 64 && k.T <= 256 && S >= 2 && S < 65536 &&
+        maxbytes + 4.0 * BK * (d->lda > d->ldb ? d->lda : d->ldb) < 4.0e9) {
+      out.lean = 4;
+      k.ktab = d->ktab;
+      k.ksl = S;
+      k.ksl_magic = (unsigned)(((1ull << 32) + (unsigned)S - 1) / (unsigned)S);
+      if (out.tag[0]) strncat(out.tag, " live", sizeof(out.tag) - strlen(out.tag) - 1);
+    }
   }
   if (out.lean) {
     int sh = 0;
@@ -1453,7 +1515,8 @@ static int launch_plan(GemmPlan& pl, hipStream_t st) {
       if (pl.lean == 3) MMNAS_LAUNCH((gemm_kernel<64, 64, true, false, true, 3, 0, 2, false, 3>), grid, block, 0, st, k);
       else if (pl.lean == 1) MMNAS_LAUNCH((gemm_kernel<64, 64, true, false, true, 3, 0, 2, false, 1>), grid, block, 0, st, k);
       else MMNAS_LAUNCH((gemm_kernel<64, 64, true, false, true, 3, 0, 2, false, 2>), grid, block, 0, st, k);
-    } else MMNAS_LAUNCH((gemm_kernel<64, 64, false, false, true, 3, 0, 2, false, 1>), grid, block, 0, st, k);
+    } else if (pl.lean == 4) MMNAS_LAUNCH((gemm_kernel<64, 64, false, false, true, 3, 0, 2, false, 4>), grid, block, 0, st, k);
+    else MMNAS_LAUNCH((gemm_kernel<64, 64, false, false, true, 3, 0, 2, false, 1>), grid, block, 0, st, k);
     return check_launch("gemm");
   }
   if (pl.big) {
@@ -1503,7 +1566,7 @@ int gemm_pair_aux(const mmnas_gemm_desc* dgrad, const mmnas_gemm_desc* wgrad, co
   } else if (aux && (rc = launch_aux_reduce(*aux, st))) return rc;
   const int naux8 = (ak.njobs + 7) / 8 * 8;
   char tag[96] = "";
-  if (prof_enabled()) snprintf(tag, sizeof(tag), "PAIR %.44s | %.40s", p0.tag, p1.tag);
+  if (prof_enabled()) snprintf(tag, sizeof(tag), p1.k.ktab ? "PAIR %.44s | %.35s live" : "PAIR %.44s | %.40s", p0.tag, p1.tag);   // (the mark survives the cut)
   ProfScope ps(MMNAS_K_GEMM, p0.flops + p1.flops, p0.bytes + p1.bytes, st, tag);
   const int nwg0p = (p0.nwg + 7) / 8 * 8;
   dim3 grid(naux8 + nwg0p + p1.nwg), block(256);
@@ -1511,7 +1574,12 @@ int gemm_pair_aux(const mmnas_gemm_desc* dgrad, const mmnas_gemm_desc* wgrad, co
     case 1: MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 1, 2>), grid, block, 0, st, p0.k, p1.k, p0.nwg, nwg0p, ak, naux8); break;
     case 2: MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 2>), grid, block, 0, st, p0.k, p1.k, p0.nwg, nwg0p, ak, naux8); break;
     case 3:
-      if (p0.lean == 3 && p1.lean) MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 3, 2, 3, 1>), grid, block, 0, st, p0.k, p1.k, p0.nwg, nwg0p, ak, naux8);
+      if (p1.lean == 4) {   // the weight gradient walks a live-row table
+        if (p0.lean == 3) MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 3, 2, 3, 4>), grid, block, 0, st, p0.k, p1.k, p0.nwg, nwg0p, ak, naux8);
+        else if (p0.lean == 1) MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 3, 2, 1, 4>), grid, block, 0, st, p0.k, p1.k, p0.nwg, nwg0p, ak, naux8);
+        else if (p0.lean == 2) MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 3, 2, 2, 4>), grid, block, 0, st, p0.k, p1.k, p0.nwg, nwg0p, ak, naux8);
+        else MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 3, 2, 0, 4>), grid, block, 0, st, p0.k, p1.k, p0.nwg, nwg0p, ak, naux8);
+      } else if (p0.lean == 3 && p1.lean) MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 3, 2, 3, 1>), grid, block, 0, st, p0.k, p1.k, p0.nwg, nwg0p, ak, naux8);
       else if (p0.lean == 3) MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 3, 2, 3, 0>), grid, block, 0, st, p0.k, p1.k, p0.nwg, nwg0p, ak, naux8);
       else if (p0.lean == 1 && p1.lean) MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 3, 2, 1, 1>), grid, block, 0, st, p0.k, p1.k, p0.nwg, nwg0p, ak, naux8);
       else if (p0.lean == 2 && p1.lean) MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 3, 2, 2, 1>), grid, block, 0, st, p0.k, p1.k, p0.nwg, nwg0p, ak, naux8);
@@ -1550,11 +1618,12 @@ int gemm_wgrad_aux(const mmnas_gemm_desc* wgrad, const AuxReduce* aux, hipStream
   ak.njobs = 3 * ak.ncb;
   const int naux8 = (ak.njobs + 7) / 8 * 8;
   char tag[96] = "";
-  if (prof_enabled()) snprintf(tag, sizeof(tag), "WGRAD+AUX %.60s", p1.tag);
+  if (prof_enabled()) snprintf(tag, sizeof(tag), "WGRAD+AUX %.60s%s", p1.tag, p1.k.ktab ? " live" : "");
   ProfScope ps(MMNAS_K_GEMM, p1.flops, p1.bytes, st, tag);
   dim3 grid(naux8 + p1.nwg), block(256);
   // (the first descriptor is not run -- 0 workgroups -- but keeps the second one at its kernel-argument offset)
-  if (p1.lean) MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 3, 2, 0, 1>), grid, block, 0, st, p1.k, p1.k, 0, 0, ak, naux8);
+  if (p1.lean == 4) MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 3, 2, 0, 4>), grid, block, 0, st, p1.k, p1.k, 0, 0, ak, naux8);
+  else if (p1.lean) MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 3, 2, 0, 1>), grid, block, 0, st, p1.k, p1.k, 0, 0, ak, naux8);
   else MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 3, 2>), grid, block, 0, st, p1.k, p1.k, 0, 0, ak, naux8);
   return check_launch("gemm_wgrad_aux");
 }

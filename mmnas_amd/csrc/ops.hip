@@ -291,8 +291,10 @@ struct SideQueue {
 // pair into its key / value source gradient and dWk / dWv by grouped launches behind the last guided operator's backward.
 // ln_pre (mixed chains, round 6): the LayerNorm backward already ran inside the node's mix kernel -- dz / dt of the scratch block
 // are filled and *ln_pre is the pending parameter reduction; op->dy is not read.
+// ktab (backbone chains, image stream): the live-row K-tile table of the chain's gradient rows (mmnas_wgrad_live_table) for
+// the weight gradients that reduce over the query rows; the per-operator entry point never passes one.
 static int att_bwd_impl(const mmnas_att_op* op, hipStream_t stream, SideQueue* sq, bool acc_kv = false, bool rel_defer = false, bool kv_defer = false,
-                        const AuxReduce* ln_pre = nullptr) {
+                        const AuxReduce* ln_pre = nullptr, const int* ktab = nullptr) {
   const bool side = sq != nullptr && !sq->rel_only;
   const bool side_rel = sq != nullptr;
   int rc = att_check(op, "att_op_bwd");
@@ -353,7 +355,7 @@ static int att_bwd_impl(const mmnas_att_op* op, hipStream_t stream, SideQueue* s
   // 3. dWm += dt^T att           [d,di], reduction over the Mq rows (same launch: mmnas_gemm_pair)
   gemm_init(wm, MMNAS_GEMM_TN, di, Mq, d, di, di);
   wm.g[0].M = d; wm.g[0].A[0] = dt; wm.g[0].B[0] = L.att; wm.g[0].C = op->dWm;
-  wm.accumulate = 1;
+  wm.accumulate = 1; wm.ktab = ktab;
   if (side) { if ((rc = mmnas_gemm(&g, stream))) return rc; }
   else if ((rc = gemm_pair_aux(&g, &wm, &lnred, (hipStream_t)stream))) return rc;
 
@@ -370,7 +372,7 @@ static int att_bwd_impl(const mmnas_att_op* op, hipStream_t stream, SideQueue* s
     w.g[0].M = di; w.g[0].A[0] = L.dQ; w.g[0].B[0] = op->xq;  w.g[0].C = op->dWq;
     w.g[1].M = di; w.g[1].A[0] = L.dK; w.g[1].B[0] = op->xkv; w.g[1].C = op->dWk;
     w.g[2].M = di; w.g[2].A[0] = L.dV; w.g[2].B[0] = op->xkv; w.g[2].C = op->dWv;
-    w.accumulate = 1;
+    w.accumulate = 1; w.ktab = ktab;   // (self-attention: the key rows are the query rows -- one table for the three groups)
     gemm_init(g, MMNAS_GEMM_NN, d, di, di, d, d);
     g.nseg = 3;
     g.g[0].M = Mq; g.g[0].C = op->dxq;
@@ -384,7 +386,7 @@ static int att_bwd_impl(const mmnas_att_op* op, hipStream_t stream, SideQueue* s
   } else {
     gemm_init(w, MMNAS_GEMM_TN, d, Mq, di, d, d);
     w.g[0].M = di; w.g[0].A[0] = L.dQ; w.g[0].B[0] = op->xq; w.g[0].C = op->dWq;
-    w.accumulate = 1;
+    w.accumulate = 1; w.ktab = ktab;   // (dWk / dWv below reduce over the language rows: dense)
     gemm_init(g, MMNAS_GEMM_NN, d, di, di, d, d);
     g.g[0].M = Mq; g.g[0].C = op->dxq; g.g[0].A[0] = L.dQ; g.g[0].B[0] = op->Wq;
     if (fl & MMNAS_F_RESIDUAL) { g.g[0].residual = dz; g.ldres = d; }
@@ -549,7 +551,7 @@ static int mmnas::mlp_fwd_impl(const mmnas_mlp_op* op, void* stream, bool defer_
 }
 
 namespace mmnas {
-static int mlp_bwd_impl(const mmnas_mlp_op* op, hipStream_t stream, SideQueue* sq, const AuxReduce* ln_pre = nullptr) {
+static int mlp_bwd_impl(const mmnas_mlp_op* op, hipStream_t stream, SideQueue* sq, const AuxReduce* ln_pre = nullptr, const int* ktab = nullptr) {
   const bool side = sq != nullptr && !sq->rel_only;
   int rc = mlp_check(op, "mlp_op_bwd");
   if (rc) return rc;
@@ -600,7 +602,7 @@ static int mlp_bwd_impl(const mmnas_mlp_op* op, hipStream_t stream, SideQueue* s
     mmnas_gemm_desc& w = wd[i];
     gemm_init(w, MMNAS_GEMM_TN, nin, M, nout, nin, nin);
     w.g[0].M = nout; w.g[0].A[0] = dpre; w.g[0].B[0] = hin; w.g[0].C = op->dW[i];
-    w.accumulate = 1;
+    w.accumulate = 1; w.ktab = ktab;
     gemm_init(g, MMNAS_GEMM_NN, nin, nout, nout, nin, nin);
     g.g[0].M = M; g.g[0].A[0] = dpre; g.g[0].B[0] = op->W[i];
     if (i == 0) {
@@ -650,7 +652,7 @@ namespace mmnas {
 struct ChainLayout {
   size_t y[MMNAS_CHAIN_MAX_OPS], save[MMNAS_CHAIN_MAX_OPS], ws[MMNAS_CHAIN_MAX_OPS], dx[MMNAS_CHAIN_MAX_OPS],
       tmp[MMNAS_CHAIN_MAX_OPS];
-  size_t dpre, encdy, relws, total;
+  size_t dpre, encdy, relws, ktab, total;
   int last_x, last_y, first_x, first_y, n_guided;
   // per operator: the operator (mixed chains: the node, named by its first operator) whose output it reads, -1 = the chain's
   // input; the node it belongs to (plain chains: itself)
@@ -771,6 +773,12 @@ static int chain_layout(const mmnas_chain* c, ChainLayout& L) {
     // one partial-sum area per node: the gate-gradient reductions of the backward are issued as ONE launch at its end
     L.mixws = take((size_t)(nodes > 0 ? nodes : 1) * mmnas_mixed_sum_ws_floats() * sizeof(float));
   }
+  // The image stream's live-row K-tile table and the live bits it is built from (mmnas_wgrad_live_table): in the input-gradient
+  // block of the stream's FIRST operator / node, which no chain, plain or mixed, ever hands out -- chain_din, the only reader
+  // of L.dx, returns dy_in for every operator whose node is the stream's first.  B Sy d floats hold the 2 ceil(B Sy / 32) + 1
+  // words for every d >= 1.  (Not a block of its own: the planners' byte counts are pinned as part of the arena contract,
+  // tests/test_abi.py.)
+  L.ktab = L.first_y >= 0 ? L.dx[L.first_y] : 0;
   L.total = off;
   return MMNAS_OK;
 }
@@ -785,12 +793,13 @@ struct BoundOp {
   mmnas_att_op a; mmnas_mlp_op m;
   AttLayout al; MlpLayout ml;      // (chain_bind with layouts = true)
   float* y;                        // the operator's own output block (plain chains: chain_out picks x_out / y_out for a stream's last)
+  const int* ktab;                 // backward, image-stream operators (mixed chains: the sampled candidate): the live-row K-tile table (else NULL)
   int flags() const { return att ? a.flags : m.flags; }
   float eps() const { return att ? a.eps : m.eps; }
 };
 static inline float* chain_buf(const mmnas_chain* c, size_t off) { return (float*)((char*)c->arena + off); }
 static void chain_bind(const mmnas_chain* c, const ChainLayout& L, int i, BoundOp& b, bool layouts = false) {
-  b.i = i; b.att = c->ops[i].kind == MMNAS_CHAIN_ATT;
+  b.i = i; b.att = c->ops[i].kind == MMNAS_CHAIN_ATT; b.ktab = nullptr;
   chain_op_shapes(c, i, b.a, b.m);
   b.y = chain_buf(c, L.y[i]);
   if (b.att) { b.a.save = chain_buf(c, L.save[i]); b.a.ws = chain_buf(c, L.ws[i]); if (layouts) b.al = att_layout(&b.a); }
@@ -806,7 +815,8 @@ static const float* chain_in(const mmnas_chain* c, const ChainLayout& L, int i) 
 }
 // the FINAL language state: the key / value source of every guided operator
 static const float* chain_x_final(const mmnas_chain* c, const ChainLayout& L) { return L.last_x >= 0 ? c->x_out : c->x_in; }
-// input-gradient buffer of operator i (mixed chains: of its node, kept in the sampled candidate i's block)
+// input-gradient buffer of operator i (mixed chains: of its node, kept in the sampled candidate i's block).  L.dx[L.first_y] is
+// never handed out here -- the image stream's first node writes dy_in -- and is TAKEN: it holds the live-row table (chain_layout)
 static float* chain_din(const mmnas_chain* c, const ChainLayout& L, int i) {
   return L.head[i] == L.first_x ? c->dx_in : (L.head[i] == L.first_y ? c->dy_in : chain_buf(c, L.dx[i]));
 }
@@ -839,7 +849,7 @@ static int chain_run_fwd(const BoundOp& b, hipStream_t s, bool defer_ln, bool* l
   return b.att ? att_fwd_impl(&b.a, s, defer_ln, ln_done, rel_ready, kv_ready) : mlp_fwd_impl(&b.m, s, defer_ln, ln_done);
 }
 static int chain_run_bwd(const BoundOp& b, hipStream_t s, SideQueue* sq, bool rel_defer, bool kv_defer, const AuxReduce* ln_pre = nullptr) {
-  return b.att ? att_bwd_impl(&b.a, s, sq, !(b.a.flags & MMNAS_F_SELF), rel_defer, kv_defer, ln_pre) : mlp_bwd_impl(&b.m, s, sq, ln_pre);
+  return b.att ? att_bwd_impl(&b.a, s, sq, !(b.a.flags & MMNAS_F_SELF), rel_defer, kv_defer, ln_pre, b.ktab) : mlp_bwd_impl(&b.m, s, sq, ln_pre, b.ktab);
 }
 // Where candidate i's LayerNorm runs, forward and backward (att_ln_place; an MLP candidate with a LayerNorm never normalises
 // itself in a mixed chain: mlp_fwd_impl keeps the general path under defer_ln), and with it what the node epilogue reads for the
@@ -853,6 +863,93 @@ static LnPlace chain_cand_view(const BoundOp& b, const float** z, const float** 
   else { *z = b.ml.z; *la = b.m.ln_a; *lb = b.m.ln_b; }
   return p;
 }
+
+// ---- live-row K-tile table of a padded batch's gradient rows ----
+// The reference computes the padding rows and masks them as KEYS in every attention and in AttFlat, so the gradient that enters
+// the decoder chain is exactly 0 on every padded row, and every operator a chain can hold keeps such a row at exactly 0 (the MLP
+// family and LayerNorm work row by row; a zero dO row gives a zero dQ row, a masked key P = 0 and with it zero dK / dV rows).
+// The weight gradients dW += dY^T X then reduce over rows that contribute exact zeros.  The table names the 32-row K-tiles that
+// hold every live row -- greedy cover, the next tile starts on the first live row not yet covered -- and the split-K products walk
+// only those (gemm.hip, mmnas_gemm_desc::ktab).  Dead rows are established from the data at every call: row r is dead iff its
+// mask byte is set AND all d values are +-0 (sign bit cleared; NaN / Inf make a row live), so a caller whose gradient is not
+// zero under the mask keeps those rows.
+// One launch: wave w of the grid decides rows 32 w .. 32 w + 31 (the values of the masked rows only, 16-byte buffer loads with
+// the unmasked rows' offsets out of range: no memory request) and publishes their live bits; the last workgroup to arrive
+// (arrival counter of the stream's stream-K workspace, left at zero) walks the bit words with one wave: lane l holds rows
+// 64 l .. 64 l + 63 and 4096 + 64 l .., every step is a readlane, a shift and a find-first-bit.
+constexpr int LIVE_MAX_ROWS = 8192;
+int sk_workspace(hipStream_t st, float** ws, size_t* ws_floats, int** cnt, int* ncnt);   // gemm.hip
+typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+
+__global__ void __launch_bounds__(256) wgrad_live_kernel(const float* __restrict__ dy, const uint8_t* __restrict__ mask, const int M, const int d,
+                                                         int* __restrict__ tab, unsigned* __restrict__ bits, const int nwords, int* __restrict__ cnt) {
+  __shared__ int s_last;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int w = blockIdx.x * 4 + wave;
+  if (w < nwords) {
+    const int r0 = w * 32;
+    const int r = r0 + (lane & 31);
+    const bool in = lane < 32 && r < M;
+    const bool masked = in && mask[r] != 0;
+    const unsigned need = (unsigned)__ballot(masked);            // rows whose values decide
+    unsigned live = (unsigned)__ballot(in && !masked);
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)dy, 0, (unsigned)M * (unsigned)d * 4u, 0x00020000);
+    for (int c0 = 0; c0 < d; c0 += 256) {
+      const int col = c0 + lane * 4;
+#pragma unroll
+      for (int hb = 0; hb < 2; ++hb) {
+        u32x4_t v[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int rr = hb * 16 + i;
+          const bool ld = ((need >> rr) & 1u) != 0 && col < d;
+          v[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, ld ? (unsigned)((r0 + rr) * d + col) * 4u : ~0u, 0, 0);
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const bool nz = ((v[i].x | v[i].y | v[i].z | v[i].w) & 0x7fffffffu) != 0;
+          if (__ballot(nz) != 0) live |= 1u << (hb * 16 + i);
+        }
+      }
+    }
+    if (lane == 0) __hip_atomic_store(bits + w, live, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the words have been written through ...
+  __syncthreads();                                    // ... before the workgroup announces its arrival
+  if (tid == 0) s_last = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
+  __syncthreads();
+  if (!s_last || wave != 0) return;
+  if (lane == 0) __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
+  unsigned wd[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int i = 2 * lane + (j & 1) + 128 * (j >> 1);
+    wd[j] = i < nwords ? __hip_atomic_load(bits + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+  }
+  int count = 0, pos = 0;
+  while (pos < M) {
+    const int wi = pos >> 6, sl = wi & 63;
+    const unsigned lo = wi < 64 ? __builtin_amdgcn_readlane(wd[0], sl) : __builtin_amdgcn_readlane(wd[2], sl);
+    const unsigned hi = wi < 64 ? __builtin_amdgcn_readlane(wd[1], sl) : __builtin_amdgcn_readlane(wd[3], sl);
+    const unsigned long long m = (((unsigned long long)hi << 32) | lo) >> (pos & 63);
+    if (m == 0) { pos = (wi + 1) << 6; continue; }
+    const int r = pos + __builtin_ctzll(m);
+    if (lane == 0) tab[1 + count] = r;
+    ++count;
+    pos = r + 32;
+  }
+  if (lane == 0) tab[0] = count;
+}
+
+static int live_table_launch(const float* dy, const uint8_t* mask, int M, int d, int* tab, hipStream_t st) {
+  const int nwords = cdiv(M, 32);
+  float* ws; size_t wsf; int* cnt; int ncnt;
+  const int rc = sk_workspace(st, &ws, &wsf, &cnt, &ncnt);
+  if (rc) return rc;
+  MMNAS_LAUNCH(wgrad_live_kernel, dim3(cdiv(nwords, 4)), dim3(256), 0, st, dy, mask, M, d, tab, (unsigned*)(tab + 1 + nwords), nwords, cnt + ncnt - 1);
+  return check_launch("wgrad_live_table");
+}
+static bool live_table_fits(long M, int d) { return M > 0 && M <= LIVE_MAX_ROWS && d > 0 && d % 4 == 0 && (double)M * d * 4.0 < 4.0e9; }
 
 // ---- side stream + events, one set per (device, main stream) ----
 struct SideCtx { hipStream_t side; hipStream_t enc; hipEvent_t ev[MMNAS_CHAIN_MAX_OPS + 2]; hipEvent_t ovl[4]; bool used; };
@@ -1086,6 +1183,14 @@ extern "C" int mmnas_set_guided_hoist(int on) { return mmnas::sw::guided_hoist.s
 extern "C" int mmnas_set_rel_hoist(int on) { return mmnas::sw::rel_hoist.set(on != 0); }
 extern "C" int mmnas_set_chain_overlap(int on) { return mmnas::sw::chain_overlap.set(on != 0); }
 
+extern "C" int mmnas_set_wgrad_live(int on) { return sw::wgrad_live.set(on != 0); }
+extern "C" int mmnas_wgrad_live_table_ints(int M) { return M > 0 ? 2 * cdiv(M, 32) + 1 : 1; }
+extern "C" int mmnas_wgrad_live_table(const float* dy, const unsigned char* mask, int M, int d, int* tab, void* stream) {
+  MMNAS_REQUIRE(dy && mask && tab, MMNAS_E_ARG, "wgrad_live_table: null pointer");
+  MMNAS_REQUIRE(live_table_fits(M, d), MMNAS_E_SHAPE, "wgrad_live_table: M=%d (1..%d) d=%d (a multiple of 4)", M, LIVE_MAX_ROWS, d);
+  return live_table_launch(dy, mask, M, d, tab, (hipStream_t)stream);
+}
+
 extern "C" int mmnas_chain_plan(const mmnas_chain* c, size_t* arena_bytes) {
   int rc = chain_check(c, "chain_plan");
   if (rc) return rc;
@@ -1132,12 +1237,26 @@ struct ChainBwd {
   size_t ex;
   const float* enc_grad = nullptr;   // set by the hoisted launch: the encoder's output gradient, complete
   SideCtx* rel_bwd_side = nullptr;   // set when the image stream's relation backward went to the side stream: joined below
+  const int* ktab = nullptr;         // live-row K-tile table of the image stream's gradient rows (chain_live_table); NULL: dense
 };
+// The chain's table (plain and mixed chains), or NULL (*out) where the dense walk stays: no mask, the ragged stream, no
+// image-stream operator, a shape the kernel does not take, MMNAS_WGRAD_LIVE=0.
+static int chain_live_table(const mmnas_chain* c, const ChainLayout& L, hipStream_t st, const int** out) {
+  *out = nullptr;
+  if (!c->y_mask || c->y_off || L.first_y < 0 || !sw::wgrad_live.get() || !live_table_fits((long)c->B * c->Sy, c->d)) return MMNAS_OK;
+  int* tab = (int*)chain_buf(c, L.ktab);
+  const int rc = live_table_launch(c->dy_out, c->y_mask, c->B * c->Sy, c->d, tab, st);
+  if (!rc) *out = tab;
+  return rc;
+}
 // hoist: relation and guided hoists allowed (not under the encoder / decoder overlap of a plain chain)
 static int chain_bwd_begin(ChainBwd& S, const mmnas_chain* c, const ChainLayout& L, hipStream_t st, SideQueue* sq, bool hoist) {
   S.c = c; S.L = &L; S.st = st; S.sq = sq;
   S.dpre = chain_buf(c, L.dpre); S.encdy = chain_buf(c, L.encdy);
   S.ex = (size_t)c->B * c->Sx * c->d;
+  // before any operator's backward launch, on the caller's stream: a side stream's queued products run behind an event that
+  // this stream records later
+  if (int r = chain_live_table(c, L, st, &S.ktab)) return r;
   if (hoist) chain_rel_groups(c, L, true, S.RG);
   chain_guided_set(c, true, hoist, S.GS);
   S.G = -1;
@@ -1350,6 +1469,7 @@ static int chain_bwd_mixed(const mmnas_chain* c, hipStream_t st, const ChainLayo
     // does not take the one-launch short-sequence backward, which does its own.  Otherwise the mix kernel hands on the
     // gradient of the candidate's output and the candidate's backward starts at its LayerNorm.
     BoundOp& b = cand[act_op - i0];
+    if (c->ops[act_op].on_y) b.ktab = S.ktab;   // (the node's mix kernel and its LayerNorm backward work row by row: dead rows stay +-0)
     float* dx = chain_bind_bwd(b, c, L, dact);
     NodeLnBwd lnb;
     lnb.dz = nullptr;
@@ -1462,6 +1582,7 @@ extern "C" int mmnas_chain_bwd(const mmnas_chain* c, void* stream) {
   auto run = [&](int i, hipStream_t s, const float* dyi, const float** dxo) -> int {
     BoundOp b;
     chain_bind(c, L, i, b);
+    if (c->ops[i].on_y) b.ktab = S.ktab;
     float* dx = chain_bind_bwd(b, c, L, dyi);
     int r;
     if ((r = chain_run_bwd(b, s, sq, S.RG.hoisted[i], S.GS.hoisted[i]))) return r;

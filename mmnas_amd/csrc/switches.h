@@ -50,6 +50,7 @@ struct Switch {
   X(rel_fwd_valu, "MMNAS_REL_FWD_VALU", 0, exact1, every_call, "1: a lone RelSelfAtt computes its bias with the per-operator fused kernel instead of the one-operator multi kernel (A/B)") \
   X(side_prio, "MMNAS_SIDE_PRIO", 1, bool, every_call, "0: the chains' extra streams without stream priorities (read when a stream pair is created)") \
   X(side_flush, "MMNAS_SIDE_FLUSH", 0, string, once, "op: side-stream parameter-gradient work released behind every operator instead of once per phase") \
+  X(wgrad_live, "MMNAS_WGRAD_LIVE", 1, int, once, "image-stream weight gradients of a padded batch's chain reduce over the 32-row K-tiles that cover the live gradient rows only (mmnas_set_wgrad_live); 0: all B Sy rows") \
   /* small.hip: short-sequence operators */ \
   X(small_ops, "MMNAS_SMALL_OPS", 1, bool, once, "SelfAtt of <= 16 rows as one launch forward (mmnas_set_small_ops); 0: the general path") \
   X(small_bwd, "MMNAS_SMALL_BWD", 1, bool, once, "the same operators' backward as two launches (mmnas_set_small_bwd)") \
