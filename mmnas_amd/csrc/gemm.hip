@@ -1162,8 +1162,8 @@ __global__ void __launch_bounds__(256, NS ? MMNAS_OCC_NS : MMNAS_OCC64) gemm_pai
 //      are ordered, so they can share it; two streams must not) ----
 // Tuning / test knobs (the MMNAS_GEMM_* rows of switches.h), read from the environment once; mmnas_gemm_reload_tuning()
 // re-reads them.
-struct Tuning { int tile, generic, sk, wgs, min_units, gm, xcd, split, pair, split_slots, split_p, pf, wide_min, split_minwg, hyb_t, lean, lean_maxb; bool loaded; };
-static Tuning g_tune = {0, 0, 1, 0, 4, 0, 1, 3, 1, 0, 24, 2, 200, 256, 16, 3, 8 << 20, false};
+struct Tuning { int tile, generic, sk, wgs, min_units, gm, xcd, split, pair, split_slots, split_p, pf, split_minwg, hyb_t, lean, lean_maxb; bool loaded; };
+static Tuning g_tune = {0, 0, 1, 0, 4, 0, 1, 3, 1, 0, 24, 2, 256, 16, 3, 8 << 20, false};
 static void load_tuning() {
   g_tune.tile = sw::gemm_tile.reload();
   g_tune.generic = sw::gemm_generic.reload();
@@ -1182,7 +1182,6 @@ static void load_tuning() {
   g_tune.split_minwg = sw::gemm_split_minwg.reload();
   g_tune.pf = sw::gemm_pf.reload() == 1 ? 1 : 2;        // register stages of operand prefetch (64^2 fp32 path)
   g_tune.hyb_t = sw::gemm_hyb_t.reload();
-  g_tune.wide_min = sw::gemm_wide_min.reload();
   g_tune.lean = sw::gemm_lean.reload();
   g_tune.lean_maxb = sw::gemm_lean_maxb.reload();
   g_tune.loaded = true;
@@ -1225,40 +1224,70 @@ int sk_workspace(hipStream_t st, float** ws, size_t* ws_floats, int** cnt, int* 
   return MMNAS_OK;
 }
 
-template <int BM, int BN, bool FAST, int NS, int PF = 1>
-static int launch(GemmK& k, int layout, int nwg, hipStream_t st) {
-  dim3 grid(nwg), block(256);
-  switch (layout) {
-    case MMNAS_GEMM_NT: MMNAS_LAUNCH((gemm_kernel<BM, BN, true, true, FAST, NS, 0, PF>), grid, block, 0, st, k); break;
-    case MMNAS_GEMM_NN: MMNAS_LAUNCH((gemm_kernel<BM, BN, true, false, FAST, NS, 0, PF>), grid, block, 0, st, k); break;
-    default: MMNAS_LAUNCH((gemm_kernel<BM, BN, false, false, FAST, NS, 0, PF>), grid, block, 0, st, k); break;
-  }
-  return check_launch("gemm");
+// ---- kernel variants ----
+// Which instantiation of gemm_kernel / gemm_pair_kernel a product runs on is one record, GemmVariant.  choose_variant() and
+// lean_level() fill it at plan time (lstm_step_plan overrides it, pair_lean0 maps two plans onto the pair kernel); a launch only
+// looks it up in the row lists below.  A new variant = one row here + one clause in the function that decides it.  A variant
+// without a row is an error at launch that names it, never a neighbouring kernel.
+struct GemmVariant { int bm, bn, layout, fast, ns, epi, pf, bdma, lean; };   // gemm_kernel's template arguments (layout: AKC, BKC)
+constexpr bool FAST = true, GENERIC = false, DMA = true, NODMA = false;
+constexpr int NT = MMNAS_GEMM_NT, NN = MMNAS_GEMM_NN, TN = MMNAS_GEMM_TN;
+constexpr u64 variant_key(const GemmVariant v) {
+  return (u64)v.bm | (u64)v.bn << 8 | (u64)v.layout << 16 | (u64)v.fast << 20 | (u64)v.ns << 24 | (u64)v.epi << 28 | (u64)v.pf << 32 | (u64)v.bdma << 36 | (u64)v.lean << 40;
 }
+constexpr u64 pair_key(int ns, int pf, int lean0, int lean1) { return (u64)ns | (u64)pf << 4 | (u64)lean0 << 8 | (u64)lean1 << 12; }
 
-}  // namespace mmnas
+// X(BM, BN, layout, FAST, NS, EPI, PF, BDMA, LEAN); ALL3: a plain product's kernel in its three layouts
+#define GEMM_ALL3(X, bt, fast, ns, pf) X(bt, bt, NT, fast, ns, 0, pf, NODMA, 0) X(bt, bt, NN, fast, ns, 0, pf, NODMA, 0) X(bt, bt, TN, fast, ns, 0, pf, NODMA, 0)
+#define GEMM_ROWS(X) \
+  GEMM_ALL3(X, 128, FAST, 1, 1) GEMM_ALL3(X, 128, FAST, 2, 1) GEMM_ALL3(X, 128, FAST, 3, 1) GEMM_ALL3(X, 128, FAST, 0, 1) GEMM_ALL3(X, 128, GENERIC, 0, 1) \
+  GEMM_ALL3(X, 64, FAST, 1, 2) GEMM_ALL3(X, 64, FAST, 2, 1) GEMM_ALL3(X, 64, FAST, 3, 2) GEMM_ALL3(X, 64, FAST, 3, 1) \
+  GEMM_ALL3(X, 64, FAST, 0, 2) GEMM_ALL3(X, 64, FAST, 0, 1) GEMM_ALL3(X, 64, GENERIC, 0, 1) \
+  X(64, 64, NT, FAST, 3, 0, 1, DMA, 0)   /* B = pre-split bf16 planes */ \
+  X(64, 64, NT, FAST, 3, 0, 2, NODMA, 1) X(64, 64, NT, FAST, 3, 0, 2, NODMA, 2) X(64, 64, TN, FAST, 3, 0, 2, NODMA, 1) X(64, 64, TN, FAST, 3, 0, 2, NODMA, 4) \
+  X(64, 64, NN, FAST, 3, 0, 2, NODMA, 1) X(64, 64, NN, FAST, 3, 0, 2, NODMA, 2) X(64, 64, NN, FAST, 3, 0, 2, NODMA, 3) \
+  X(64, 64, NT, FAST, 0, 1, 1, NODMA, 0) X(64, 64, NN, FAST, 0, 2, 1, NODMA, 0)   /* LSTM time steps */
+// X(NS, PF, LEAN0, LEAN1) of gemm_pair_kernel<64, 64, ...>
+#define PAIR_ROWS(X) \
+  X(0, 1, 0, 0) X(0, 2, 0, 0) X(1, 2, 0, 0) X(2, 1, 0, 0) X(3, 1, 0, 0) X(3, 2, 0, 0) \
+  X(3, 2, 2, 0) X(3, 2, 3, 0) X(3, 2, 0, 1) X(3, 2, 1, 1) X(3, 2, 2, 1) X(3, 2, 3, 1) \
+  X(3, 2, 0, 4) X(3, 2, 1, 4) X(3, 2, 2, 4) X(3, 2, 3, 4)
 
-using namespace mmnas;
+typedef void (*GemmFn)(const GemmK);
+typedef void (*PairFn)(const GemmK, const GemmK, const int, const int, const AuxReduceK, const int);
+template <class Fn> struct VariantRow { u64 key; Fn fn; };
+#define X(bm, bn, lay, fast, ns, epi, pf, dma, lean) \
+  {variant_key({bm, bn, lay, fast, ns, epi, pf, dma, lean}), gemm_kernel<bm, bn, lay != TN, lay == NT, fast, ns, epi, pf, dma, lean>},
+static constexpr VariantRow<GemmFn> GEMM_TABLE[] = {GEMM_ROWS(X)};
+#undef X
+#define X(ns, pf, lean0, lean1) {pair_key(ns, pf, lean0, lean1), gemm_pair_kernel<64, 64, ns, pf, lean0, lean1>},
+static constexpr VariantRow<PairFn> PAIR_TABLE[] = {PAIR_ROWS(X)};
+#undef X
 
-extern "C" int mmnas_gemm_reload_tuning(void) {
-  load_tuning();
-  return MMNAS_OK;
+template <class Fn, int N>
+constexpr bool keys_unique(const VariantRow<Fn> (&t)[N]) {
+  for (int i = 0; i < N; ++i)
+    for (int j = i + 1; j < N; ++j) if (t[i].key == t[j].key) return false;
+  return true;
 }
+static_assert(keys_unique(GEMM_TABLE) && keys_unique(PAIR_TABLE), "two rows of a kernel table share a variant key");
 
-namespace mmnas {
+template <class Fn, int N>
+static Fn find_kernel(const VariantRow<Fn> (&t)[N], u64 key) {   // (a linear scan: ~60 rows against a 4 us launch)
+  for (int i = 0; i < N; ++i) if (t[i].key == key) return t[i].fn;
+  return nullptr;
+}
 
 struct GemmPlan {
   GemmK k;
-  int nwg, layout;
-  bool big, fast, wide;   // big: 128^2 tiles; wide: 128 x 64 tiles (BM x BN); neither: 64^2
-  bool bdma;              // B = pre-split bf16 planes, loaded by LDS-DMA (NT, 64^2, bf16x6)
-  int lean;               // the lean kernel (gemm_body<..., LEAN>): 1 whole tiles (NT / NN) or split-K pieces (TN), 2 hybrid / stream-K
+  int nwg;
+  GemmVariant v;          // the kernel it runs on
   double flops, bytes;
   char tag[96];
 };
 
-static int plan_gemm(const mmnas_gemm_desc* d, hipStream_t st, GemmPlan& out) {
-  if (!g_tune.loaded) load_tuning();
+// plan_gemm, part 1: the descriptor's checks, its operands copied into k, and whether the buffer-load path is legal (*fast)
+static int plan_operands(const mmnas_gemm_desc* d, GemmK& k, bool* fast_out, double* maxbytes_out, double* sumM_out) {
   MMNAS_REQUIRE(d != nullptr, MMNAS_E_ARG, "mmnas_gemm: null descriptor");
   MMNAS_REQUIRE(d->ngroups >= 1 && d->ngroups <= MAXG && d->nseg >= 1 && d->nseg <= 3, MMNAS_E_ARG,
                 "mmnas_gemm: ngroups=%d nseg=%d out of range", d->ngroups, d->nseg);
@@ -1272,8 +1301,6 @@ static int plan_gemm(const mmnas_gemm_desc* d, hipStream_t st, GemmPlan& out) {
     for (int g = 0; g < d->ngroups; ++g)
       MMNAS_REQUIRE(!d->g[g].gate, MMNAS_E_ARG, "mmnas_gemm: no gate epilogue when accumulating onto C");
   }
-
-  GemmK& k = out.k;
   memset(&k, 0, sizeof(k));
   k.ngroups = d->ngroups; k.nseg = d->nseg; k.N = d->N; k.K = d->K;
   k.lda = d->lda; k.ldb = d->ldb; k.ldc = d->ldc; k.ldres = d->ldres; k.ldgate = d->ldgate;
@@ -1315,11 +1342,17 @@ static int plan_gemm(const mmnas_gemm_desc* d, hipStream_t st, GemmPlan& out) {
   // (TN: both operands are [K][rows]; a K that is no multiple of the K-tile simply ends inside the last tile, whose rows
   //  behind K lie outside the operands' buffer ranges and read as zero -- the row count of a PACKED ragged batch is
   //  arbitrary, and it is the reduction length of every weight gradient)
-  bool fast = avec && bvec && (d->K % BK == 0 || tn) && maxbytes < 4.0e9;
-  if (g_tune.generic) fast = false;
+  *fast_out = avec && bvec && (d->K % BK == 0 || tn) && maxbytes < 4.0e9 && !g_tune.generic;
+  *maxbytes_out = maxbytes; *sumM_out = sumM;
+  return MMNAS_OK;
+}
+
+// plan_gemm, part 2: the schedule -- tile shape (*big: 128^2, else 64^2), mode, units per workgroup P, grid (*nwg_out) -- from
+// the descriptor's sizes and the tuning values alone.  Fills the schedule fields of k; the stream-K workspace is the caller's.
+static int plan_schedule(const mmnas_gemm_desc* d, GemmK& k, bool* big_out, int* nwg_out) {
+  const bool accumulate = k.accumulate != 0;
   k.ntk = cdiv(d->K, BK);
   k.T = k.ntk * d->nseg;
-
   // ---- schedule: tile shape, K-slices S, units per workgroup P ----
   // Measured on the VQA shapes (tools/gemm_bench.py, profiles/):
   //   * 128^2 tiles move half the LDS / L2 bytes per flop of 64^2 ones (123-134 vs 96-119 TF/s) but only pay
@@ -1340,27 +1373,18 @@ static int plan_gemm(const mmnas_gemm_desc* d, hipStream_t st, GemmPlan& out) {
   const int min_units = g_tune.min_units;
   bool big = ntiles_for(128) >= 2048;
   if (g_tune.tile == 128) big = true;
-  if (g_tune.tile == 64 || g_tune.tile == 12864) big = false;
-  // 128 x 64 tiles (each wave two 32x32 MFMA tiles down the rows): 1.33x the products per operand byte and per barrier
-  // of 64^2 -- for plain products on the buffer-load path whose rows fill the chip anyway (experiment: MMNAS_GEMM_TILE=12864)
-  bool wide = !big && g_tune.tile == 12864 && !accumulate && fast && g_tune.split != 2 && g_tune.split != 1;
-  if (wide) {
-    long n = 0;
-    for (int g = 0; g < d->ngroups; ++g) n += (long)cdiv(d->g[g].M, 128) * cdiv(d->N, 64);
-    if (n < g_tune.wide_min) wide = false;
-  }
-  const int bt = big ? 128 : 64;            // tile height (rows) unless wide
-  const int btm = wide ? 128 : bt, btn = bt;
-  k.tiles_n = cdiv(d->N, btn);
+  if (g_tune.tile == 64) big = false;
+  const int bt = big ? 128 : 64;
+  k.tiles_n = cdiv(d->N, bt);
   long t0 = 0;
   for (int g = 0; g < MAXG; ++g) k.gtile0[g] = INT_MAX;
-  for (int g = 0; g < d->ngroups; ++g) { k.g[g].tile0 = k.gtile0[g] = (int)t0; t0 += (long)cdiv(d->g[g].M, btm) * k.tiles_n; }
+  for (int g = 0; g < d->ngroups; ++g) { k.g[g].tile0 = k.gtile0[g] = (int)t0; t0 += (long)cdiv(d->g[g].M, bt) * k.tiles_n; }
   MMNAS_REQUIRE(t0 < (1l << 30), MMNAS_E_SHAPE, "mmnas_gemm: too many output tiles");
   k.ntiles = (int)t0;
   k.gm = g_tune.gm > 0 ? g_tune.gm : 8;
   k.xcd_remap = g_tune.xcd;
   // co-resident workgroups: 256 CUs x 2 (128^2 tiles: 72 KB LDS each) or x 4
-  const int slots = g_tune.wgs > 0 ? (g_tune.wgs < MAX_WGS ? g_tune.wgs : MAX_WGS) : ((big || wide) ? 512 : 1024);
+  const int slots = g_tune.wgs > 0 ? (g_tune.wgs < MAX_WGS ? g_tune.wgs : MAX_WGS) : (big ? 512 : 1024);
   // how evenly whole tiles load the 256 CUs: mean / max tiles per CU (the dispatcher balances dynamically)
   const double per_cu = (double)k.ntiles / 256.0;
   const double dp_eff = per_cu / (double)(long)(per_cu + 0.999999);
@@ -1388,7 +1412,7 @@ static int plan_gemm(const mmnas_gemm_desc* d, hipStream_t st, GemmPlan& out) {
       k.mode = MODE_SPLIT;
       nwg = S * k.ntiles;
     }
-  } else if (!accumulate && sk != 0 && !big && !wide && U < (1ll << 30) && k.ntiles <= MAX_CNT_TILES && g_tune.wgs == 0 &&
+  } else if (!accumulate && sk != 0 && !big && U < (1ll << 30) && k.ntiles <= MAX_CNT_TILES && g_tune.wgs == 0 &&
              sk == 1 && k.ntiles > 256 && k.ntiles < 8192 && k.ntiles % 256 != 0 && k.T >= g_tune.hyb_t) {
     // Single round (every tile resident at once, 3-4 workgroups per CU) with a ragged last "layer": the first
     // floor(ntiles / 256) * 256 tiles are computed whole; the R tail tiles are streamed by ~one extra SHORT workgroup
@@ -1407,7 +1431,7 @@ static int plan_gemm(const mmnas_gemm_desc* d, hipStream_t st, GemmPlan& out) {
     k.U = (int)Ut;
     nwg = n_full + n_sk;
   } else if (!accumulate && sk != 0 && U < (1ll << 30) && k.ntiles <= MAX_CNT_TILES && k.T >= 2 * min_units &&
-             (sk == 2 || (!big && !wide && ((dp_eff < 0.6 && k.T >= 16) || (dp_eff < 0.9 && k.T >= 48))))) {
+             (sk == 2 || (!big && ((dp_eff < 0.6 && k.T >= 16) || (dp_eff < 0.9 && k.T >= 48))))) {
     // (runs of >= 8 K-tiles when the choice is automatic: fewer contributors per tile in the hand-over, measured
     //  5-20 % faster than 4 on the M = 896 products)
     const int smu = sk == 2 ? min_units : 2 * min_units;
@@ -1422,37 +1446,29 @@ static int plan_gemm(const mmnas_gemm_desc* d, hipStream_t st, GemmPlan& out) {
       nwg = (int)((U + P - 1) / P);
     }
   }
-  if (k.mode == MODE_STREAM) {
-    SkWorkspace w;
-    const int rc = get_workspace(st, &w);
-    if (rc) return rc;
-    k.ws = w.ws; k.cnt = w.cnt;
-  }
-  // algorithmic work: 2*M*N*K flops per product; minimum traffic = operands once + result once
-  out.tag[0] = 0;
-  if (prof_enabled())
-    snprintf(out.tag, sizeof(out.tag), "%s M=%d/%d/%d N=%d K=%d seg=%d t%d wg=%d P=%d/%d %s%s", tn ? "TN" : (bkc ? "NT" : "NN"),
-             d->g[0].M, d->ngroups > 1 ? d->g[1].M : 0, d->ngroups > 2 ? d->g[2].M : 0, d->N, d->K, d->nseg, wide ? 12864 : bt, nwg, k.P, k.T,
-             k.mode == MODE_TILE ? "tile" : (k.mode == MODE_SPLIT ? "split" : (k.n_full ? "hybrid" : "stream")),
-             fast ? (g_tune.split == 2 ? " bf16x3" : (g_tune.split == 3 ? " bf16x6" : (g_tune.split == 1 ? " bf16x1" : ""))) : " generic");
-  out.flops = 2.0 * sumM * d->N * d->K * d->nseg;
-  out.bytes = 4.0 * (sumM * d->K * d->nseg + (double)d->N * d->K * d->nseg * d->ngroups + sumM * d->N);
-  out.nwg = nwg; out.layout = d->layout; out.big = big; out.fast = fast; out.wide = wide;
-  out.bdma = d->b_planes != 0;
-  if (out.bdma) {
-    // B[i] of every group = mmnas_split_planes output ([3][N][ldb] bf16).  One kernel shape exists for it; anything else
-    // would read the planes as fp32: refuse.
-    MMNAS_REQUIRE(d->layout == MMNAS_GEMM_NT && fast && !big && !wide && !accumulate && g_tune.split == 3 && d->N % 64 == 0 &&
-                  (d->ldb % 8) == 0, MMNAS_E_ARG,
-                  "mmnas_gemm: b_planes needs layout NT, 64^2 tiles on the buffer-load path, N %% 64 == 0, ldb %% 8 == 0, MMNAS_GEMM_SPLIT=6 "
-                  "(N=%d K=%d ldb=%d)", d->N, d->K, d->ldb);
-    if (out.tag[0]) strncat(out.tag, " Bdma", sizeof(out.tag) - strlen(out.tag) - 1);
-  }
-  // ---- the lean kernel: whole tiles of an NT / NN product on the default split-operand path whose epilogue operands can be
-  //      moved as 16-byte rows and whose B matrix an XCD's L2 holds beside the A panels in flight ----
-  out.lean = 0;
-  const bool lean_base = fast && !big && !wide && !out.bdma && g_tune.split == 3 && g_tune.pf == 2 &&
-                         (k.tiles_n & (k.tiles_n - 1)) == 0 && d->ldc % 4 == 0;
+  *big_out = big; *nwg_out = nwg;
+  return MMNAS_OK;
+}
+
+// The kernel of a plain product, before lean_level() has its say.  The rules, each with its reason:
+static GemmVariant choose_variant(int layout, bool fast, bool big, bool bdma) {
+  const int bt = big ? 128 : 64;
+  const int ns = fast ? g_tune.split : 0;   // bf16 parts per operand; odd shapes on the guarded-load path stay on the fp32 MFMA
+  // register stages of operand prefetch.  The second stage exists on the 64^2 buffer-load path only (gemm_body's static_assert):
+  // 128^2 tiles and the guarded-load path have one.  bf16x1 keeps only its two-stage kernel, bf16x3 was never given one;
+  // bf16x6 and fp32 have both and follow MMNAS_GEMM_PF.  B as pre-split bf16 planes (bdma) has one kernel shape: NT 64^2
+  // bf16x6 with one stage (plan_gemm has refused every other shape).
+  const int pf = big || !fast || bdma ? 1 : (ns == 1 ? 2 : (ns == 2 ? 1 : g_tune.pf));
+  return {bt, bt, layout, fast, ns, /* epi (1, 2: the LSTM time steps, lstm_step_plan) */ 0, pf, bdma, /* lean */ 0};
+}
+
+// plan_gemm, part 3: the lean kernel (gemm_body<..., LEAN>) this product may run on, 0 for the general one.  Lean kernels are
+// 64^2, bf16x6, two prefetch stages: v must already say so.  NT: 1 whole tiles, 2 hybrid / stream-K; NN: the same and 3 = whole
+// tiles with column sums; TN: 1 split-K pieces, 4 = those walking a live-row table.  NT / NN: products on the default split-operand
+// path whose epilogue operands can be moved as 16-byte rows and whose B matrix an XCD's L2 holds beside the A panels in flight.
+static int lean_level(const mmnas_gemm_desc* d, const GemmK& k, const GemmVariant& v, int nwg, double maxbytes) {
+  const bool tn = d->layout == MMNAS_GEMM_TN;
+  const bool lean_base = v.bm == 64 && v.ns == 3 && v.pf == 2 && !v.bdma && (k.tiles_n & (k.tiles_n - 1)) == 0 && d->ldc % 4 == 0;
   if (lean_base && (g_tune.lean & 1) && !tn && k.mode != MODE_SPLIT && d->N % 4 == 0 && 4.0 * d->N * d->K * d->nseg <= (double)g_tune.lean_maxb) {
     bool ok = true, any_colsum = false;
     for (int g = 0; g < d->ngroups && ok; ++g) {
@@ -1464,76 +1480,91 @@ static int plan_gemm(const mmnas_gemm_desc* d, hipStream_t st, GemmPlan& out) {
            (!s.residual || (((uintptr_t)s.residual & 15) == 0 && d->ldres % 4 == 0 && rows * d->ldres * 4.0 < 4.0e9)) &&
            (!s.gate || (((uintptr_t)s.gate & 15) == 0 && d->ldgate % 4 == 0 && rows * d->ldgate * 4.0 < 4.0e9));
     }
-    out.lean = ok ? (k.mode == MODE_TILE ? 1 : 2) : 0;
     // column sums: the element-wise lean form (NN, whole tiles) or the general kernel
-    if (any_colsum) out.lean = (ok && k.mode == MODE_TILE && d->layout == MMNAS_GEMM_NN) ? 3 : 0;
-  } else if (lean_base && tn && k.mode == MODE_SPLIT && d->nseg == 1 && (g_tune.lean & 2) && k.ntiles >= 2 && k.ntiles < 65536 && nwg < 65536) {
+    if (any_colsum) return (ok && k.mode == MODE_TILE && d->layout == MMNAS_GEMM_NN) ? 3 : 0;
+    return ok ? (k.mode == MODE_TILE ? 1 : 2) : 0;
+  }
+  if (lean_base && tn && k.mode == MODE_SPLIT && d->nseg == 1 && (g_tune.lean & 2) && k.ntiles >= 2 && k.ntiles < 65536 && nwg < 65536) {
     // weight gradients: split-K pieces added by buffer atomics; nothing else rides on them
-    bool ok = true;
-    for (int g = 0; g < d->ngroups && ok; ++g) {
+    for (int g = 0; g < d->ngroups; ++g) {
       const mmnas_gemm_group& s = d->g[g];
-      ok = !s.bias && !s.residual && !s.gate && !s.colsum && ((double)s.M + 1.0) * d->ldc * 4.0 < 4.0e9;
+      if (s.bias || s.residual || s.gate || s.colsum || !(((double)s.M + 1.0) * d->ldc * 4.0 < 4.0e9)) return 0;
     }
-    out.lean = ok ? 1 : 0;
-    if (ok) k.nt_magic = (unsigned)(((1ull << 32) + (unsigned)k.ntiles - 1) / (unsigned)k.ntiles);
     // live-row table: pieces of at most 64 K-tiles (one start row per lane) out of at most 256 (four table words per lane),
     // at least two slices (ksl_magic = ceil(2^32 / S) does not fit 32 bits for S = 1; MODE_SPLIT has S >= 2 today);
     // a tile that starts on the operand's last row ends 31 rows behind it -- still a 32-bit byte offset
     const int S = nwg / k.ntiles;
-    if (ok && d->ktab && k.P <= 64 && k.T <= 256 && S >= 2 && S < 65536 &&
-        maxbytes + 4.0 * BK * (d->lda > d->ldb ? d->lda : d->ldb) < 4.0e9) {
-      out.lean = 4;
+    return d->ktab && k.P <= 64 && k.T <= 256 && S >= 2 && S < 65536 && maxbytes + 4.0 * BK * (d->lda > d->ldb ? d->lda : d->ldb) < 4.0e9 ? 4 : 1;
+  }
+  return 0;
+}
+
+static int plan_gemm(const mmnas_gemm_desc* d, hipStream_t st, GemmPlan& out) {
+  if (!g_tune.loaded) load_tuning();
+  GemmK& k = out.k;
+  bool fast, big; double maxbytes, sumM; int rc, nwg;
+  if ((rc = plan_operands(d, k, &fast, &maxbytes, &sumM))) return rc;
+  if ((rc = plan_schedule(d, k, &big, &nwg))) return rc;
+  if (k.mode == MODE_STREAM) {
+    SkWorkspace w;
+    if ((rc = get_workspace(st, &w))) return rc;
+    k.ws = w.ws; k.cnt = w.cnt;
+  }
+  const bool tn = d->layout == MMNAS_GEMM_TN;
+  // algorithmic work: 2*M*N*K flops per product; minimum traffic = operands once + result once
+  out.tag[0] = 0;
+  if (prof_enabled())
+    snprintf(out.tag, sizeof(out.tag), "%s M=%d/%d/%d N=%d K=%d seg=%d t%d wg=%d P=%d/%d %s%s", tn ? "TN" : (d->layout == MMNAS_GEMM_NT ? "NT" : "NN"),
+             d->g[0].M, d->ngroups > 1 ? d->g[1].M : 0, d->ngroups > 2 ? d->g[2].M : 0, d->N, d->K, d->nseg, big ? 128 : 64, nwg, k.P, k.T,
+             k.mode == MODE_TILE ? "tile" : (k.mode == MODE_SPLIT ? "split" : (k.n_full ? "hybrid" : "stream")),
+             fast ? (g_tune.split == 2 ? " bf16x3" : (g_tune.split == 3 ? " bf16x6" : (g_tune.split == 1 ? " bf16x1" : ""))) : " generic");
+  out.flops = 2.0 * sumM * d->N * d->K * d->nseg;
+  out.bytes = 4.0 * (sumM * d->K * d->nseg + (double)d->N * d->K * d->nseg * d->ngroups + sumM * d->N);
+  out.nwg = nwg;
+  if (d->b_planes) {
+    // B[i] of every group = mmnas_split_planes output ([3][N][ldb] bf16).  One kernel shape exists for it; anything else
+    // would read the planes as fp32: refuse.
+    MMNAS_REQUIRE(d->layout == MMNAS_GEMM_NT && fast && !big && !k.accumulate && g_tune.split == 3 && d->N % 64 == 0 &&
+                  (d->ldb % 8) == 0, MMNAS_E_ARG,
+                  "mmnas_gemm: b_planes needs layout NT, 64^2 tiles on the buffer-load path, N %% 64 == 0, ldb %% 8 == 0, MMNAS_GEMM_SPLIT=6 "
+                  "(N=%d K=%d ldb=%d)", d->N, d->K, d->ldb);
+    if (out.tag[0]) strncat(out.tag, " Bdma", sizeof(out.tag) - strlen(out.tag) - 1);
+  }
+  GemmVariant& v = out.v;
+  v = choose_variant(d->layout, fast, big, d->b_planes != 0);
+  v.lean = lean_level(d, k, v, nwg, maxbytes);
+  if (v.lean) {
+    while ((1 << k.tn_shift) < k.tiles_n) ++k.tn_shift;
+    if (tn) k.nt_magic = (unsigned)(((1ull << 32) + (unsigned)k.ntiles - 1) / (unsigned)k.ntiles);
+    if (v.lean == 4) {
       k.ktab = d->ktab;
-      k.ksl = S;
-      k.ksl_magic = (unsigned)(((1ull << 32) + (unsigned)S - 1) / (unsigned)S);
+      k.ksl = nwg / k.ntiles;
+      k.ksl_magic = (unsigned)(((1ull << 32) + (unsigned)k.ksl - 1) / (unsigned)k.ksl);
       if (out.tag[0]) strncat(out.tag, " live", sizeof(out.tag) - strlen(out.tag) - 1);
     }
-  }
-  if (out.lean) {
-    int sh = 0;
-    while ((1 << sh) < k.tiles_n) ++sh;
-    k.tn_shift = sh;
     if (out.tag[0]) strncat(out.tag, " lean", sizeof(out.tag) - strlen(out.tag) - 1);
   }
   return MMNAS_OK;
 }
 
-static int launch_plan(GemmPlan& pl, hipStream_t st) {
-  GemmK& k = pl.k;
+static int launch_plan(GemmPlan& pl, hipStream_t st, const char* who = "gemm") {
+  const GemmVariant& v = pl.v;
+  const GemmFn fn = find_kernel(GEMM_TABLE, variant_key(v));
+  MMNAS_REQUIRE(fn, MMNAS_E_ARG, "%s: no kernel for variant {tile %dx%d layout %d fast %d ns %d epi %d pf %d bdma %d lean %d}", who, v.bm, v.bn,
+                v.layout, v.fast, v.ns, v.epi, v.pf, v.bdma, v.lean);
   ProfScope ps(MMNAS_K_GEMM, pl.flops, pl.bytes, st, pl.tag);
-  const int ns = pl.fast ? g_tune.split : 0;   // (odd shapes on the guarded-load path stay on the fp32 MFMA)
-  if (pl.bdma) {
-    MMNAS_LAUNCH((gemm_kernel<64, 64, true, true, true, 3, 0, 1, true>), dim3(pl.nwg), dim3(256), 0, st, k);
-    return check_launch("gemm");
-  }
-  if (pl.lean) {
-    const dim3 grid(pl.nwg), block(256);
-    if (pl.layout == MMNAS_GEMM_NT) {
-      if (pl.lean == 1) MMNAS_LAUNCH((gemm_kernel<64, 64, true, true, true, 3, 0, 2, false, 1>), grid, block, 0, st, k);
-      else MMNAS_LAUNCH((gemm_kernel<64, 64, true, true, true, 3, 0, 2, false, 2>), grid, block, 0, st, k);
-    } else if (pl.layout == MMNAS_GEMM_NN) {
-      if (pl.lean == 3) MMNAS_LAUNCH((gemm_kernel<64, 64, true, false, true, 3, 0, 2, false, 3>), grid, block, 0, st, k);
-      else if (pl.lean == 1) MMNAS_LAUNCH((gemm_kernel<64, 64, true, false, true, 3, 0, 2, false, 1>), grid, block, 0, st, k);
-      else MMNAS_LAUNCH((gemm_kernel<64, 64, true, false, true, 3, 0, 2, false, 2>), grid, block, 0, st, k);
-    } else if (pl.lean == 4) MMNAS_LAUNCH((gemm_kernel<64, 64, false, false, true, 3, 0, 2, false, 4>), grid, block, 0, st, k);
-    else MMNAS_LAUNCH((gemm_kernel<64, 64, false, false, true, 3, 0, 2, false, 1>), grid, block, 0, st, k);
-    return check_launch("gemm");
-  }
-  if (pl.big) {
-    if (ns == 1) return launch<128, 128, true, 1>(k, pl.layout, pl.nwg, st);
-    if (ns == 2) return launch<128, 128, true, 2>(k, pl.layout, pl.nwg, st);
-    if (ns == 3) return launch<128, 128, true, 3>(k, pl.layout, pl.nwg, st);
-    return pl.fast ? launch<128, 128, true, 0>(k, pl.layout, pl.nwg, st) : launch<128, 128, false, 0>(k, pl.layout, pl.nwg, st);
-  }
-  if (pl.wide) return ns == 3 ? launch<128, 64, true, 3>(k, pl.layout, pl.nwg, st) : launch<128, 64, true, 0, 2>(k, pl.layout, pl.nwg, st);
-  if (ns == 1) return launch<64, 64, true, 1, 2>(k, pl.layout, pl.nwg, st);
-  if (ns == 2) return launch<64, 64, true, 2>(k, pl.layout, pl.nwg, st);
-  if (ns == 3) return g_tune.pf == 2 ? launch<64, 64, true, 3, 2>(k, pl.layout, pl.nwg, st) : launch<64, 64, true, 3>(k, pl.layout, pl.nwg, st);
-  if (pl.fast && g_tune.pf == 2) return launch<64, 64, true, 0, 2>(k, pl.layout, pl.nwg, st);
-  return pl.fast ? launch<64, 64, true, 0>(k, pl.layout, pl.nwg, st) : launch<64, 64, false, 0>(k, pl.layout, pl.nwg, st);
+  MMNAS_LAUNCH(fn, dim3(pl.nwg), dim3(256), 0, st, pl.k);
+  return check_launch(who);
 }
 
 }  // namespace mmnas
+
+using namespace mmnas;
+
+extern "C" int mmnas_gemm_reload_tuning(void) {
+  load_tuning();
+  return MMNAS_OK;
+}
 
 extern "C" int mmnas_gemm(const mmnas_gemm_desc* d, void* stream) {
   GemmPlan pl;
@@ -1543,22 +1574,34 @@ extern "C" int mmnas_gemm(const mmnas_gemm_desc* d, void* stream) {
 }
 
 namespace mmnas {
+// The (LEAN0, LEAN1) of the pair kernel for a data gradient planned at lean level l0 (0 when there is none) next to a weight
+// gradient at l1 (0, 1 or 4).  Every combination has its row except (1, 0): level 2 (hybrid / stream-K) contains level 1 (whole
+// tiles), so that one runs as (2, 0) and no (1, 0) instantiation is kept.
+static int pair_lean0(int l0, int l1) { return l0 == 1 && l1 == 0 ? 2 : l0; }
+
+// The data gradient (NN) and the weight gradient (TN) of a linear layer in one launch, a pending column reduction riding on it
+// as a few extra workgroups.  dgrad == NULL: the weight gradient alone carries the reduction (the short-sequence backward of
+// small.hip leaves no NN product to pair with).
 int gemm_pair_aux(const mmnas_gemm_desc* dgrad, const mmnas_gemm_desc* wgrad, const AuxReduce* aux, hipStream_t st) {
   GemmPlan p0, p1;
   int rc;
-  if ((rc = plan_gemm(dgrad, st, p0))) return rc;
+  if (dgrad && (rc = plan_gemm(dgrad, st, p0))) return rc;
   if ((rc = plan_gemm(wgrad, st, p1))) return rc;
-  // one launch when both run on the 64^2 buffer-load kernel and the second one needs no workspace of its own
-  const bool pair = g_tune.pair && p0.fast && p1.fast && !p0.big && !p1.big && !p0.wide && !p1.wide && p0.layout == MMNAS_GEMM_NN &&
-                    p1.layout == MMNAS_GEMM_TN && p1.k.mode != MODE_STREAM;
-  if (!pair) {
+  const GemmVariant& v1 = p1.v;
+  const bool ride = aux && aux->part && g_tune.pair != 3;   // (MMNAS_GEMM_PAIR=3: pending reductions get their own launch)
+  // one launch when both run on the 64^2 buffer-load kernel and the second one needs no workspace of its own; without a data
+  // gradient, when there is a reduction to carry and the default kernel (bf16x6, two prefetch stages) to carry it
+  bool one = g_tune.pair && v1.fast && v1.bm == 64 && v1.layout == MMNAS_GEMM_TN && p1.k.mode != MODE_STREAM;
+  if (dgrad) one = one && p0.v.fast && p0.v.bm == 64 && p0.v.layout == MMNAS_GEMM_NN;
+  else one = one && ride && v1.ns == 3 && v1.pf == 2;
+  if (!one) {
     if (aux && (rc = launch_aux_reduce(*aux, st))) return rc;
-    if ((rc = launch_plan(p0, st))) return rc;
+    if (dgrad && (rc = launch_plan(p0, st))) return rc;
     return launch_plan(p1, st);
   }
   AuxReduceK ak;
   memset(&ak, 0, sizeof(ak));
-  if (aux && aux->part && g_tune.pair != 3) {   // (MMNAS_GEMM_PAIR=3: pending reductions get their own launch)
+  if (ride) {
     ak.part = aux->part; ak.nrows = aux->nrows; ak.d = aux->d;
     for (int i = 0; i < 3; ++i) ak.out[i] = aux->out[i];
     ak.ncb = cdiv(aux->d, 16);
@@ -1566,70 +1609,25 @@ int gemm_pair_aux(const mmnas_gemm_desc* dgrad, const mmnas_gemm_desc* wgrad, co
   } else if (aux && (rc = launch_aux_reduce(*aux, st))) return rc;
   const int naux8 = (ak.njobs + 7) / 8 * 8;
   char tag[96] = "";
-  if (prof_enabled()) snprintf(tag, sizeof(tag), p1.k.ktab ? "PAIR %.44s | %.35s live" : "PAIR %.44s | %.40s", p0.tag, p1.tag);   // (the mark survives the cut)
-  ProfScope ps(MMNAS_K_GEMM, p0.flops + p1.flops, p0.bytes + p1.bytes, st, tag);
-  const int nwg0p = (p0.nwg + 7) / 8 * 8;
-  dim3 grid(naux8 + nwg0p + p1.nwg), block(256);
-  switch (g_tune.split) {
-    case 1: MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 1, 2>), grid, block, 0, st, p0.k, p1.k, p0.nwg, nwg0p, ak, naux8); break;
-    case 2: MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 2>), grid, block, 0, st, p0.k, p1.k, p0.nwg, nwg0p, ak, naux8); break;
-    case 3:
-      if (p1.lean == 4) {   // the weight gradient walks a live-row table
-        if (p0.lean == 3) MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 3, 2, 3, 4>), grid, block, 0, st, p0.k, p1.k, p0.nwg, nwg0p, ak, naux8);
-        else if (p0.lean == 1) MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 3, 2, 1, 4>), grid, block, 0, st, p0.k, p1.k, p0.nwg, nwg0p, ak, naux8);
-        else if (p0.lean == 2) MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 3, 2, 2, 4>), grid, block, 0, st, p0.k, p1.k, p0.nwg, nwg0p, ak, naux8);
-        else MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 3, 2, 0, 4>), grid, block, 0, st, p0.k, p1.k, p0.nwg, nwg0p, ak, naux8);
-      } else if (p0.lean == 3 && p1.lean) MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 3, 2, 3, 1>), grid, block, 0, st, p0.k, p1.k, p0.nwg, nwg0p, ak, naux8);
-      else if (p0.lean == 3) MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 3, 2, 3, 0>), grid, block, 0, st, p0.k, p1.k, p0.nwg, nwg0p, ak, naux8);
-      else if (p0.lean == 1 && p1.lean) MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 3, 2, 1, 1>), grid, block, 0, st, p0.k, p1.k, p0.nwg, nwg0p, ak, naux8);
-      else if (p0.lean == 2 && p1.lean) MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 3, 2, 2, 1>), grid, block, 0, st, p0.k, p1.k, p0.nwg, nwg0p, ak, naux8);
-      else if (p0.lean) MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 3, 2, 2, 0>), grid, block, 0, st, p0.k, p1.k, p0.nwg, nwg0p, ak, naux8);
-      else if (p1.lean) MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 3, 2, 0, 1>), grid, block, 0, st, p0.k, p1.k, p0.nwg, nwg0p, ak, naux8);
-      else if (g_tune.pf == 2) MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 3, 2>), grid, block, 0, st, p0.k, p1.k, p0.nwg, nwg0p, ak, naux8);
-      else MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 3>), grid, block, 0, st, p0.k, p1.k, p0.nwg, nwg0p, ak, naux8);
-      break;
-    default:
-      if (g_tune.pf == 2) MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 0, 2>), grid, block, 0, st, p0.k, p1.k, p0.nwg, nwg0p, ak, naux8);
-      else MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 0>), grid, block, 0, st, p0.k, p1.k, p0.nwg, nwg0p, ak, naux8);
-      break;
+  if (prof_enabled()) {
+    if (dgrad) snprintf(tag, sizeof(tag), p1.k.ktab ? "PAIR %.44s | %.35s live" : "PAIR %.44s | %.40s", p0.tag, p1.tag);   // (the mark survives the cut)
+    else snprintf(tag, sizeof(tag), "WGRAD+AUX %.60s%s", p1.tag, p1.k.ktab ? " live" : "");
   }
-  return check_launch("gemm_pair");
-}
-}  // namespace mmnas
-
-namespace mmnas {
-// A weight-gradient product (TN, split-K) with a pending column reduction riding on its launch as a few extra workgroups:
-// gemm_pair_aux without the data-gradient half (the short-sequence backward of small.hip leaves no NN product to pair with).
-int gemm_wgrad_aux(const mmnas_gemm_desc* wgrad, const AuxReduce* aux, hipStream_t st) {
-  GemmPlan p1;
-  int rc;
-  if ((rc = plan_gemm(wgrad, st, p1))) return rc;
-  const bool ride = aux && aux->part && g_tune.pair && g_tune.pair != 3 && g_tune.split == 3 && g_tune.pf == 2 && p1.fast && !p1.big && !p1.wide &&
-                    p1.layout == MMNAS_GEMM_TN && p1.k.mode != MODE_STREAM;
-  if (!ride) {
-    if (aux && (rc = launch_aux_reduce(*aux, st))) return rc;
-    return launch_plan(p1, st);
-  }
-  AuxReduceK ak;
-  memset(&ak, 0, sizeof(ak));
-  ak.part = aux->part; ak.nrows = aux->nrows; ak.d = aux->d;
-  for (int i = 0; i < 3; ++i) ak.out[i] = aux->out[i];
-  ak.ncb = cdiv(aux->d, 16);
-  ak.njobs = 3 * ak.ncb;
-  const int naux8 = (ak.njobs + 7) / 8 * 8;
-  char tag[96] = "";
-  if (prof_enabled()) snprintf(tag, sizeof(tag), "WGRAD+AUX %.60s%s", p1.tag, p1.k.ktab ? " live" : "");
-  ProfScope ps(MMNAS_K_GEMM, p1.flops, p1.bytes, st, tag);
-  dim3 grid(naux8 + p1.nwg), block(256);
-  // (the first descriptor is not run -- 0 workgroups -- but keeps the second one at its kernel-argument offset)
-  if (p1.lean == 4) MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 3, 2, 0, 4>), grid, block, 0, st, p1.k, p1.k, 0, 0, ak, naux8);
-  else if (p1.lean) MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 3, 2, 0, 1>), grid, block, 0, st, p1.k, p1.k, 0, 0, ak, naux8);
-  else MMNAS_LAUNCH((gemm_pair_kernel<64, 64, 3, 2>), grid, block, 0, st, p1.k, p1.k, 0, 0, ak, naux8);
-  return check_launch("gemm_wgrad_aux");
+  ProfScope ps(MMNAS_K_GEMM, (dgrad ? p0.flops : 0.0) + p1.flops, (dgrad ? p0.bytes : 0.0) + p1.bytes, st, tag);
+  // (without a data gradient the first descriptor is not run -- 0 workgroups -- but keeps the second one at its kernel-argument offset)
+  const GemmK& k0 = dgrad ? p0.k : p1.k;
+  const int nwg0 = dgrad ? p0.nwg : 0, nwg0p = (nwg0 + 7) / 8 * 8;
+  const int l0 = pair_lean0(dgrad ? p0.v.lean : 0, v1.lean);
+  const char* who = dgrad ? "gemm_pair" : "gemm_wgrad_aux";
+  const PairFn fn = find_kernel(PAIR_TABLE, pair_key(v1.ns, v1.pf, l0, v1.lean));
+  MMNAS_REQUIRE(fn, MMNAS_E_ARG, "%s: no kernel for variant {ns %d pf %d lean0 %d lean1 %d}", who, v1.ns, v1.pf, l0, v1.lean);
+  MMNAS_LAUNCH(fn, dim3(naux8 + nwg0p + p1.nwg), dim3(256), 0, st, k0, p1.k, nwg0, nwg0p, ak, naux8);
+  return check_launch(who);
 }
 }  // namespace mmnas
 
 extern "C" int mmnas_gemm_pair(const mmnas_gemm_desc* dgrad, const mmnas_gemm_desc* wgrad, void* stream) {
+  MMNAS_REQUIRE(dgrad != nullptr, MMNAS_E_ARG, "mmnas_gemm: null descriptor");
   return gemm_pair_aux(dgrad, wgrad, nullptr, (hipStream_t)stream);
 }
 
@@ -1674,10 +1672,12 @@ extern "C" int mmnas_split_planes(const float* w, void* planes, size_t n, void* 
 // ------------------------------------------------------------------------------------------
 namespace mmnas {
 // units_per_wg: 0 = whole tiles, one per workgroup; > 0 = stream-K runs of that many K-tiles
-static int lstm_step_plan(GemmPlan& pl, const mmnas_gemm_desc& d, hipStream_t st, const char* who, int units_per_wg) {
+static int lstm_step_plan(GemmPlan& pl, const mmnas_gemm_desc& d, hipStream_t st, const char* who, int epi, int units_per_wg) {
   int rc = plan_gemm(&d, st, pl);
   if (rc) return rc;
-  MMNAS_REQUIRE(pl.fast && !pl.big && !pl.wide, MMNAS_E_SHAPE, "%s: shape outside the step kernel's range (hidden size %% 32 == 0, aligned buffers)", who);
+  MMNAS_REQUIRE(pl.v.fast && pl.v.bm == 64, MMNAS_E_SHAPE, "%s: shape outside the step kernel's range (hidden size %% 32 == 0, aligned buffers)", who);
+  // the step epilogues exist on one kernel: 64^2, buffer loads, fp32 MFMA, one prefetch stage -- whatever the split knob says
+  pl.v.ns = 0; pl.v.epi = epi; pl.v.pf = 1; pl.v.bdma = 0; pl.v.lean = 0;
   GemmK& k = pl.k;
   k.n_full = k.full_per = k.sk_per = 0;
   if (units_per_wg <= 0 || units_per_wg >= k.T) {
@@ -1715,13 +1715,12 @@ extern "C" int mmnas_lstm_fwd(const float* x_tm, const float* Wih, const float* 
     d.ldres = 4 * H; d.alpha = 1.f; d.gate_scale = 1.f; d.split_k = 1;
     d.g[0].M = B; d.g[0].A[0] = Hall + t * bh; d.g[0].B[0] = Whh; d.g[0].C = Hall + (t + 1) * bh; d.g[0].residual = xp + t * bg;
     GemmPlan pl;
-    if ((rc = lstm_step_plan(pl, d, st, "lstm_fwd", sw::lstm_fwd_p.get()))) return rc;
+    if ((rc = lstm_step_plan(pl, d, st, "lstm_fwd", 1, sw::lstm_fwd_p.get()))) return rc;
     pl.k.lg_cprev = Call + t * bh; pl.k.lg_cout = Call + (t + 1) * bh; pl.k.lg_gates = Gall + t * bg;
     pl.k.lg_h2 = out + (size_t)t * H; pl.k.lg_ldh2 = T * H;
-    ProfScope ps(MMNAS_K_GEMM, pl.flops, pl.bytes, st, pl.tag);
-    MMNAS_LAUNCH((gemm_kernel<64, 64, true, true, true, 0, 1>), dim3(pl.nwg), dim3(256), 0, st, pl.k);
+    if ((rc = launch_plan(pl, st, "lstm_fwd"))) return rc;
   }
-  return check_launch("lstm_fwd");
+  return MMNAS_OK;
 }
 
 extern "C" int mmnas_lstm_bwd(const float* dout, const float* Whh, const float* Call, const float* Gall, float* DG, float* dc,
@@ -1739,13 +1738,12 @@ extern "C" int mmnas_lstm_bwd(const float* dout, const float* Whh, const float* 
     d.g[0].M = B; d.g[0].A[0] = DG + (t + 1) * bg; d.g[0].B[0] = Whh; d.g[0].C = scratch; d.g[0].residual = dout + (size_t)t * H;
     GemmPlan pl;
     int rc;
-    if ((rc = lstm_step_plan(pl, d, st, "lstm_bwd", sw::lstm_bwd_p.get()))) return rc;
+    if ((rc = lstm_step_plan(pl, d, st, "lstm_bwd", 2, sw::lstm_bwd_p.get()))) return rc;
     pl.k.lg_act = Gall + t * bg; pl.k.lg_c = Call + (t + 1) * bh; pl.k.lg_cprev = Call + t * bh;
     pl.k.lg_dc = dc; pl.k.lg_gates = DG + t * bg;
-    ProfScope ps(MMNAS_K_GEMM, pl.flops, pl.bytes, st, pl.tag);
-    MMNAS_LAUNCH((gemm_kernel<64, 64, true, false, true, 0, 2>), dim3(pl.nwg), dim3(256), 0, st, pl.k);
+    if ((rc = launch_plan(pl, st, "lstm_bwd"))) return rc;
   }
-  return check_launch("lstm_bwd");
+  return MMNAS_OK;
 }
 
 #ifdef MMNAS_DBG_STAMP

@@ -327,7 +327,7 @@ static int att_bwd_impl(const mmnas_att_op* op, hipStream_t stream, SideQueue* s
     AuxReduce red;
     red.part = norm ? L.lnws : nullptr; red.nrows = op->B; red.d = d;
     red.out[0] = op->dln_a; red.out[1] = op->dln_b; red.out[2] = nullptr;
-    return gemm_wgrad_aux(&w4, &red, stream);
+    return gemm_pair_aux(nullptr, &w4, &red, stream);
   }
 
   // 1. through LayerNorm and the output dropout

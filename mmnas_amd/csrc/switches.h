@@ -87,7 +87,6 @@ struct Switch {
   X(gemm_split_minwg, "MMNAS_GEMM_SPLIT_MINWG", 256, int, reload, "fewest split-K pieces in total when pieces of SPLIT_P would be fewer") \
   X(gemm_pf, "MMNAS_GEMM_PF", 2, int, reload, "1 | 2: K-tiles of operand loads in flight ahead of the MFMA block (64^2 fp32 path)") \
   X(gemm_hyb_t, "MMNAS_GEMM_HYB_T", 16, int, reload, "fewest K-tiles per output tile for the whole-tiles + streamed-tail hybrid") \
-  X(gemm_wide_min, "MMNAS_GEMM_WIDE_MIN", 200, int, reload, "fewest 128x64 tiles for that shape to be chosen") \
   X(gemm_lean, "MMNAS_GEMM_LEAN", 3, int, reload, "lean kernels: bit 0 NT / NN products, bit 1 split-K TN products") \
   X(gemm_lean_maxb, "MMNAS_GEMM_LEAN_MAXB", 8 << 20, int, reload, "largest B matrix (bytes) the lean tile order is used for") \
   X(lstm_fwd_p, "MMNAS_LSTM_FWD_P", 0, int, every_call, "K-tiles per workgroup of the LSTM forward step's stream-K product (0: whole tiles; read per time step)") \

@@ -238,13 +238,16 @@ def test_gemm_bf16_split_stream_k_and_epilogue(mode, gemm_tuning):
         assert rel_err(Cs[i].cpu().numpy(), ref.numpy()) < (2e-5 if mode == 3 else 3e-6)
 
 
-@pytest.mark.parametrize('M,nin,nout', [(6400, 512, 512), (896, 256, 1024), (300, 132, 68), (6400, 2048, 512), (64, 32, 32)])
+@pytest.mark.parametrize('M,nin,nout', [(6400, 512, 512), (896, 256, 1024), (300, 132, 68), (6400, 2048, 512), (64, 32, 32),
+                                        (1152, 512, 1408)])
 @pytest.mark.parametrize('pair', [1, 0])
 @pytest.mark.parametrize('split', [0, 6])
 def test_gemm_pair_matches_two_launches(M, nin, nout, pair, split, gemm_tuning):
     """mmnas_gemm_pair (data gradient NN + weight gradient TN of one linear layer in one launch, the second section
     behind the first): grouped weight gradients, K segments, residual and gate epilogues on the data gradient;
-    odd shapes fall back to two launches inside the call.  Same results as the fp64 products either way."""
+    odd shapes fall back to two launches inside the call.  Same results as the fp64 products either way.
+    (1152, 512, 1408): the three-segment data gradient's B matrices exceed what the lean kernel takes while the weight gradient
+    stays lean -- the pair kernel's (general, lean) form, which no other shape here selects."""
     from mmnas_amd import ops
     import mmnas_amd._lib as L
     gemm_tuning(pair=pair, split=split)

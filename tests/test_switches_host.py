@@ -94,7 +94,7 @@ def test_defaults_with_nothing_set():
             'GEMM_LN_MINM': 2048, 'GEMM_LN_MAXK': 256, 'MHA_NW': 4, 'MHA_PAIR': 1, 'MHA_BWD_FUSED': 1, 'MHA_FWD_B16': 1,
             'MHA_BWD_B16': 1, 'REL_MULTI_YIELD': 0, 'REL_BWD_VALU': 1, 'GEMM_TILE': 0, 'GEMM_GENERIC': 0, 'GEMM_SK': 1,
             'GEMM_MIN_UNITS': 4, 'GEMM_XCD': 1, 'GEMM_PAIR': 1, 'GEMM_SPLIT_P': 24, 'GEMM_SPLIT_MINWG': 256, 'GEMM_HYB_T': 16,
-            'GEMM_WIDE_MIN': 200, 'GEMM_LEAN_MAXB': 8 << 20, 'LSTM_FWD_P': 0, 'LSTM_BWD_P': 8}
+            'GEMM_LEAN_MAXB': 8 << 20, 'LSTM_FWD_P': 0, 'LSTM_BWD_P': 8}
     for k, v in want.items():
         assert t['MMNAS_' + k][1] == v, k
     py = _child('import json\nfrom mmnas_amd import switches as S\n'
