@@ -476,7 +476,10 @@ int mmnas_set_rel_overlap(int on);
  * Q [B*Sq, ldq], K,V [B*Sk, ldk/ldv], head h occupies columns [h*dh, (h+1)*dh).
 * O [B*Sq, ldo] same column convention; lse [B,H,Sq,2] = (row max, 1/row sum) of each score row
  * (saved for backward instead of the map).  dropout idx = ((b*H+h)*Sq+q)*Sk+k.
- * Limits: dh in {16,32,64,128,256}; Sk <= 256.
+ * Limits: dh in {16,32,64,128,256}; B*H*Sq*Sk < 2^32 (the dropout / bias index is 32-bit); row strides multiples of 4
+ * floats, Q / K / V 16-byte aligned; packed rows (q_off / k_off) at dh = 64 with Sq, Sk <= 128.  No limit on the key count: up
+ * to 256 keys the forward holds a query block's score row in registers, beyond it (or from MMNAS_MHA_STREAM_MINK keys on,
+ * dense rows) it streams the keys in blocks of 128 with a running maximum and sum -- the same lse, the same dropout mask.
  * bwd recomputes P from (Q,K,lse): dQ,dK,dV (same layouts as Q,K,V) are overwritten;
  * dbiasT [B,H,Sk,Sq] (nullable) receives dZ.
  * ------------------------------------------------------------------------------------------ */
@@ -518,6 +521,8 @@ int mmnas_mha_core_fwd_indexed(const mmnas_mha_desc* d, const int* kv_idx, void*
  * UniimgAtt (:415-428, caller concatenates x and y into xkv):
  *   y = LN( xq + drop( merge( att( xq Wq^T, xkv Wk^T, xkv Wv^T ) ) ) )
  * dropout sites: 0 = attention map, 1 = operator output.
+ * Any sequence length the attention core takes (above): more than 256 keys -- grid features, xkv = cat(x, y) of UniimgAtt --
+ * run the streaming forward and the general backward; the plan's bias buffers are sized B*H*Sk*Sq.
  * ------------------------------------------------------------------------------------------ */
 typedef struct mmnas_att_op {
   int B, Sq, Sk, d, di, H, dh, R;

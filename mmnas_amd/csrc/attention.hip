@@ -325,6 +325,250 @@ __global__ void __launch_bounds__(64 * NW, (NKC <= 4 && NW == 4) ? 2 : 1) mha_fw
 }
 
 // ------------------------------------------------------------------------------------------
+// forward, STREAMING: any number of keys (the kernels above hold a query block's whole score row in registers: <= 256 keys).
+// grid (ceil(Sq / 128), H, B), block 256: a wave owns 32 queries, the workgroup walks the keys in blocks of KB = 128
+// (NKC = 4 chunks of 32, the score tile of mha_fwd_body<.., 4, 4>).  Same arithmetic contract, same query-owner / transposed
+// score layout, same ballot bit masks, same dropout index, same key-major bias.
+//   * running statistics per query (one lane, both half-waves hold a copy): m = maximum so far, l = sum of exp(z - m) so far.
+//     A block that raises m multiplies l and the O accumulators by alpha = exp(m_old - m_new); the dropout multiplier goes on
+//     the unnormalised e = exp(z - m) in front of P V; 1 / l multiplies O once at the end.  stats = (final m, 1 / final l):
+//     what the backward kernels read.  alpha lives on the query's lane, the O accumulators hold the query in the register
+//     row: 16 lane reads per block, skipped (wave-uniform) when no lane's maximum moved.
+//   * masked keys are -1e9, never -inf; keys behind Sk (last block only) are -inf.  Hence, with no special case:
+//       - a fully masked row: every block has maximum -1e9, e = exp(0) = 1 per key: m = -1e9, l = Sk, a uniform map;
+//       - a block of only masked keys behind a live one: e = exp(-1e9 - m) = 0 exactly, alpha = 1: it adds nothing;
+//       - a live key behind only masked blocks: alpha = exp(-1e9 - m_new) = 0 (not NaN: both finite) wipes l and O;
+//       - the first block always holds key 0 (in range), so m is finite from the first block on: the only -inf operand of
+//         alpha is m_old of the first block, exp(-inf - finite) = 0 on l = 0 and O = 0.
+//   * ONE LDS tile image [128][DHC + 4] (34 KB) that the K and V tiles of a block pass through in turn; the Q fragments
+//     of a wave's own queries come straight from global into registers (as in mha_bwd_q_kernel).  The tile sequence
+//     K(0) V(0) K(1) V(1) ... is known in advance: the NEXT tile's loads are issued into registers (TileRegs) right behind
+//     the barrier that publishes the current one, so they fly behind its MFMAs (the round trip per phase that the one-shot
+//     forward's comments above record is paid once, for the first tile).  The bias values and mask bytes of a block are
+//     fetched in front of its K Q^T products for the same reason.
+//   * head dims: ONE PASS (running statistics + rescale) for all of 16 .. 256.  d_h <= 64 is one chunk (NCH = 1).
+//     d_h = 128 / 256 (NCH = 2 / 4 chunks of 64): a block's tile sequence is K chunks 0..NCH-1 (scores summed over the
+//     chunks), then the V chunks, each into its own pair of O accumulators, which live across the key loop.
+//       - d_h = 128: both output chunks in the workgroup (NOC = 2: 64 accumulator registers beside the 64 of the score tile);
+//         256 + 199 registers at one workgroup per CU (one wave per SIMD), no scratch.
+//       - d_h = 256: all four output chunks in one workgroup compiled to 58-97 spilled registers (220-368 bytes of scratch
+//         per lane), with or without the bias prefetch.  A two-pass form (statistics first, then P V against them) would not
+//         help: its second pass holds the same 128 accumulators.  Instead TWO workgroups per (batch, head, query block) take
+//         two output chunks each (NOC = 2, grid.y = 2 H, as the backward kernels split the head dim): each repeats the score
+//         product and arrives at the same (m, l) bit for bit; the first one writes the statistics.  6 instead of 4 products'
+//         worth of MFMA time, no scratch (256 + 201 registers).
+//     With several chunks the Q fragments of chunk c are re-read per block (L2 hits) and the bias is read where it is used.
+// No atomics, no cross-workgroup hand-off: the same inputs give the same bits.  Dense rows only (no q_off / k_off).
+// ------------------------------------------------------------------------------------------
+constexpr int MHA_STREAM_KB = 128;
+
+template <int DHC, int NCH, int NOC>
+__global__ void __launch_bounds__(256, 1) mha_fwd_stream_kernel(const MhaK p) {
+  constexpr int NW = 4, NKC = MHA_STREAM_KB / 32, KB = MHA_STREAM_KB;
+  constexpr int LD = DHC + 4, NT = 64 * NW, JC = DHC >= 32 ? DHC / 32 : 1, NS = DHC / 8;
+  constexpr bool BPF = NCH == 1;   // the block's 64 bias values per lane in flight behind its K Q^T (several chunks: the O accumulators need the registers)
+  __shared__ __attribute__((aligned(16))) float KVs[KB * LD];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l31 = lane & 31, hh = lane >> 5;
+  const int b = blockIdx.z, h = blockIdx.y % p.H, oc0 = (blockIdx.y / p.H) * NOC, q0 = blockIdx.x * 32 * NW;
+  const int Sq = p.Sq, Sk = p.Sk;
+  const bool active = q0 + 32 * w < Sq;  // wave-uniform
+  const int qi = q0 + 32 * w + l31;
+  const bool qok = qi < Sq;
+  const int qic = qok ? qi : Sq - 1;
+  const size_t bh = (size_t)b * p.H + h;
+  const size_t krow0 = (size_t)b * Sk;
+  const bool has_bias = p.biasT != nullptr, has_mask = p.mask != nullptr, has_drop = p.drop.thresh != 0;
+  const float* Kh = p.K + krow0 * p.ldk + h * p.dh;
+  const float* Vh = p.V + krow0 * p.ldv + h * p.dh + oc0 * DHC;   // this workgroup's output chunks oc0 .. oc0 + NOC - 1
+
+  float4 qfr[NS];   // B operands of S^T = K Q^T: this lane's half of its query row, head-dim chunk c (rows behind Sq: zero)
+  auto load_q = [&](int c) {
+    const float* qrow = p.Q + ((size_t)b * Sq + qic) * p.ldq + h * p.dh + c * DHC + 4 * hh;   // clamped: no branch around the loads
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      const float4 x = *reinterpret_cast<const float4*>(qrow + 8 * s);
+      qfr[s] = qok ? x : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  };
+
+  f32x16 o[NOC][JC];
+#pragma unroll
+  for (int c = 0; c < NOC; ++c)
+#pragma unroll
+    for (int jc = 0; jc < JC; ++jc)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) o[c][jc][r] = 0.f;
+  float m = -INFINITY, l = 0.f;
+  const uint32_t dpre = drop_pre(p.drop, (uint32_t)((bh * Sq + qi) * Sk + 4 * hh));
+
+  TileRegs<KB, DHC, NT> t;   // the tile behind the one in LDS
+  tile_fetch<KB, DHC, NT>(t, Kh, Sk, p.ldk, tid);
+  if (NCH == 1) load_q(0);
+
+  for (int kb = 0; kb < Sk; kb += KB) {
+    const int nk = Sk - kb;   // keys of this block and behind it (>= 1)
+    // mask bytes and bias values of the block: issued here, used behind the K Q^T products
+    bool mk[2] = {false, false};
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int key = kb + 64 * j + lane;
+      if (has_mask) mk[j] = p.mask[krow0 + (key < Sk ? key : 0)] != 0;
+    }
+    float bias[BPF ? NKC : 1][16];
+    if (BPF && has_bias && active) {
+#pragma unroll
+      for (int kc = 0; kc < NKC; ++kc)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int key = min(kb + 32 * kc + acc_row(r, hh), Sk - 1);
+          bias[BPF ? kc : 0][r] = p.biasT[(bh * Sk + key) * Sq + qic];
+        }
+    }
+
+    // ---- S^T = K Q^T over the head-dim chunks ----
+    f32x16 acc[NKC];
+#pragma unroll
+    for (int kc = 0; kc < NKC; ++kc)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[kc][r] = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      if (NCH > 1) load_q(c);
+      __syncthreads();   // every wave is done with the tile in LDS
+      tile_store<KB, DHC, NT>(t, KVs, tid);
+      __syncthreads();
+      if (c + 1 < NCH) tile_fetch<KB, DHC, NT>(t, Kh + (size_t)kb * p.ldk + (c + 1) * DHC, nk, p.ldk, tid);
+      else tile_fetch<KB, DHC, NT>(t, Vh + (size_t)kb * p.ldv, nk, p.ldv, tid);
+      if (active) {
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+          const float4 qf = qfr[s];
+#pragma unroll
+          for (int kc = 0; kc < NKC; ++kc) {
+            const float4 kf = *reinterpret_cast<const float4*>(KVs + (32 * kc + l31) * LD + 8 * s + 4 * hh);
+            MFMA4(acc[kc], kf, qf)
+          }
+        }
+      }
+    }
+
+    // ---- this block's part of the softmax: running (m, l), e = exp(z - m) left in acc ----
+    if (active) {
+      unsigned long long mbits[2], vbits[2];   // bit (kc, r): 32 (kc & 1) + (r & 3) + 8 (r >> 2) of word kc >> 1, pre-shifted per lane half
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const bool inr = kb + 64 * j + lane < Sk;
+        mbits[j] = __ballot(mk[j] && inr) >> (4 * hh);
+        vbits[j] = __ballot(inr) >> (4 * hh);
+      }
+      float bm = -INFINITY;
+#pragma unroll
+      for (int kc = 0; kc < NKC; ++kc) {
+        if (!BPF && has_bias) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int key = min(kb + 32 * kc + acc_row(r, hh), Sk - 1);
+            bias[0][r] = p.biasT[(bh * Sk + key) * Sq + qic];
+          }
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          constexpr unsigned long long one = 1ull;
+          const unsigned long long bit = one << (32 * (kc & 1) + (r & 3) + 8 * (r >> 2));
+          float v = acc[kc][r] * p.scale;
+          if (has_bias) v += bias[BPF ? kc : 0][r];
+          v = (mbits[kc >> 1] & bit) ? -1e9f : v;
+          v = (vbits[kc >> 1] & bit) ? v : -INFINITY;
+          acc[kc][r] = v;
+          bm = fmaxf(bm, v);
+        }
+      }
+      bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
+      const float mn = fmaxf(m, bm);            // finite: the block's first key is in range
+      const float alpha = __expf(m - mn);       // first block: exp(-inf) = 0 on l = 0, O = 0
+      float bs = 0.f;
+#pragma unroll
+      for (int kc = 0; kc < NKC; ++kc)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float e = __expf(acc[kc][r] - mn);   // (masked behind a live key: exp(-1e9 - m) = 0; behind Sk: exp(-inf) = 0)
+          acc[kc][r] = e;
+          bs += e;
+        }
+      bs += __shfl_xor(bs, 32, 64);
+      l = l * alpha + bs;
+      m = mn;
+      if (kb > 0 && __any(alpha != 1.f)) {   // wave-uniform
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float ar = __shfl(alpha, acc_row(r, hh), 64);   // the query of accumulator row r
+#pragma unroll
+          for (int c = 0; c < NOC; ++c)
+#pragma unroll
+            for (int jc = 0; jc < JC; ++jc) o[c][jc][r] *= ar;
+        }
+      }
+      if (has_drop) {
+        // (dropout index (bh Sq + q) Sk + key, key = kb + 32 kc + (r & 3) + 8 (r >> 2) + 4 hh)
+        const uint32_t dpb = dpre + (uint32_t)kb * DROP_G;
+#pragma unroll
+        for (int kc = 0; kc < NKC; ++kc)
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            acc[kc][r] *= drop_mult_pre(p.drop, dpb + (uint32_t)(32 * kc + (r & 3) + 8 * (r >> 2)) * DROP_G);
+      }
+    }
+
+    // ---- O += E V, head-dim chunk by chunk (E tile = the accumulators, as MFMA A operand) ----
+#pragma unroll
+    for (int c = 0; c < NOC; ++c) {
+      __syncthreads();
+      tile_store<KB, DHC, NT>(t, KVs, tid);
+      __syncthreads();
+      if (c + 1 < NOC) tile_fetch<KB, DHC, NT>(t, Vh + (size_t)kb * p.ldv + (c + 1) * DHC, nk, p.ldv, tid);
+      else if (kb + KB < Sk) tile_fetch<KB, DHC, NT>(t, Kh + (size_t)(kb + KB) * p.ldk, nk - KB, p.ldk, tid);
+      if (active) {
+#pragma unroll
+        for (int kc = 0; kc < NKC; ++kc) {
+          float bvv[16][JC];   // (read in one batch in front of the chunk's MFMAs, as in mha_fwd_body)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int key = 32 * kc + acc_row(r, hh);
+#pragma unroll
+            for (int jc = 0; jc < JC; ++jc) bvv[r][jc] = (DHC >= 32 || l31 < DHC) ? KVs[key * LD + 32 * jc + l31] : 0.f;
+          }
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+#pragma unroll
+            for (int jc = 0; jc < JC; ++jc) o[c][jc] = mfma32(acc[kc][r], bvv[r][jc], o[c][jc]);
+        }
+      }
+    }
+  }
+
+  if (!active) return;
+  const float inv = 1.0f / l;
+  if (qok && hh == 0 && oc0 == 0) {
+    p.stats[(bh * Sq + qi) * 2] = m;
+    p.stats[(bh * Sq + qi) * 2 + 1] = inv;
+  }
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const float ir = __shfl(inv, acc_row(r, hh), 64);
+    const int q = q0 + 32 * w + acc_row(r, hh);
+    if (q < Sq) {
+#pragma unroll
+      for (int c = 0; c < NOC; ++c)
+#pragma unroll
+        for (int jc = 0; jc < JC; ++jc) {
+          const int col = 32 * jc + l31;
+          if (col < DHC) p.O[((size_t)b * Sq + q) * p.ldo + h * p.dh + (oc0 + c) * DHC + col] = o[c][jc][r] * ir;
+        }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // delta[b,h,q] = sum_j dO[b,q,h,j] * O[b,q,h,j]  ( = sum_k dA[q,k] A[q,k])
 // ------------------------------------------------------------------------------------------
 __global__ void mha_delta_kernel(const float* __restrict__ dO, const float* __restrict__ O, float* __restrict__ delta,
@@ -975,7 +1219,6 @@ static int fill(const mmnas_mha_desc* d, MhaK& k, bool bwd) {
                 d->H, d->Sq, d->Sk);
   MMNAS_REQUIRE(d->dh == 16 || d->dh == 32 || d->dh == 64 || d->dh == 128 || d->dh == 256, MMNAS_E_SHAPE,
                 "mha: head dim %d not in {16,32,64,128,256}", d->dh);
-  MMNAS_REQUIRE(d->Sk <= 256, MMNAS_E_SHAPE, "mha: Sk=%d > 256 keys not supported", d->Sk);
   MMNAS_REQUIRE(d->Q && d->K && d->V && d->lse, MMNAS_E_ARG, "mha: null Q/K/V/stats");
   MMNAS_REQUIRE(d->ldq % 4 == 0 && d->ldk % 4 == 0 && d->ldv % 4 == 0 && d->ldo % 4 == 0, MMNAS_E_SHAPE,
                 "mha: row strides must be multiples of 4 floats");
@@ -1003,6 +1246,25 @@ static int fill(const mmnas_mha_desc* d, MhaK& k, bool bwd) {
 }
 
 static int mha_nw() { return sw::mha_nw.get() == 2 ? 2 : 4; }   // measured: 4-wave groups are 7-15 % faster (K/V tiles loaded half as often)
+
+// Fewest keys at which the forward streams the keys (MMNAS_MHA_STREAM_MINK, 1..257): more than 256 keys always stream; a lower
+// value runs mha_fwd_stream_kernel where the one-shot kernels serve by default (tests, tools/mha_bench.py).
+static int mha_stream_mink() {
+  const int v = sw::mha_stream_mink.get();
+  return v < 1 ? 1 : v > 257 ? 257 : v;
+}
+static bool mha_streams(const MhaK& k) { return !k.qoff && !k.koff && k.Sk >= mha_stream_mink(); }
+
+static void launch_fwd_stream(const MhaK& k, hipStream_t st) {
+  const dim3 grid(cdiv(k.Sq, 128), k.H, k.B), block(256);
+  switch (k.dh) {
+    case 16: MMNAS_LAUNCH((mha_fwd_stream_kernel<16, 1, 1>), grid, block, 0, st, k); break;
+    case 32: MMNAS_LAUNCH((mha_fwd_stream_kernel<32, 1, 1>), grid, block, 0, st, k); break;
+    case 64: MMNAS_LAUNCH((mha_fwd_stream_kernel<64, 1, 1>), grid, block, 0, st, k); break;
+    case 128: MMNAS_LAUNCH((mha_fwd_stream_kernel<64, 2, 2>), grid, block, 0, st, k); break;
+    default: MMNAS_LAUNCH((mha_fwd_stream_kernel<64, 4, 2>), dim3(grid.x, 2 * k.H, k.B), block, 0, st, k); break;   // d_h = 256: two workgroups, two output chunks each
+  }
+}
 
 template <int DHC>
 static void launch_fwd(const MhaK& k, hipStream_t st) {
@@ -1053,7 +1315,8 @@ int mha_core_fwd_pair(const mmnas_mha_desc* d0, const mmnas_mha_desc* d1, hipStr
   const bool on = sw::mha_pair.get() != 0;
   const int nkc = cdiv(k0.Sk, 32);
   const bool same = on && k0.B == k1.B && k0.H == k1.H && k0.Sq == k1.Sq && k0.Sk == k1.Sk && k0.dh == 64 && k1.dh == 64 &&
-                    nkc > 2 && nkc <= 4 && k0.Sq > 64 && mha_nw() == 4 && !k0.qoff == !k1.qoff && !k0.koff == !k1.koff;
+                    nkc > 2 && nkc <= 4 && k0.Sq > 64 && mha_nw() == 4 && !k0.qoff == !k1.qoff && !k0.koff == !k1.koff &&
+                    !mha_streams(k0) && !mha_streams(k1);   // (a lowered MMNAS_MHA_STREAM_MINK: two streaming launches)
   if (!same) {
     if ((rc = mmnas_mha_core_fwd(d0, st))) return rc;
     return mmnas_mha_core_fwd(d1, st);
@@ -1122,6 +1385,8 @@ extern "C" int mmnas_mha_core_fwd(const mmnas_mha_desc* d, void* stream) {
   const double bhqk = (double)k.B * k.H * k.Sq * k.Sk;
   ProfScope ps(MMNAS_K_MHA_FWD, 4.0 * bhqk * k.dh,
                4.0 * ((double)k.B * k.H * k.dh * (2.0 * k.Sq + 2.0 * k.Sk) + (k.biasT ? bhqk : 0.0)), st);
+  // more than 256 keys (or MMNAS_MHA_STREAM_MINK and more): the keys in blocks of 128
+  if (mha_streams(k)) { k.nch = k.dh >= 64 ? k.dh / 64 : 1; launch_fwd_stream(k, st); return check_launch("mha_core_fwd"); }
   // d_h = 64, 65..128 keys (the image stream): both products on the bf16 pipe as exactly split operands (attention_bwd16.hip)
   if (k.dh == 64 && mha_fwd_b16_launch(k.B, k.H, k.Sq, k.Sk, k.ldq, k.ldk, k.ldv, k.ldo, k.Q, k.K, k.V, k.mask, k.biasT, k.O, k.stats,
                                        k.drop, k.scale, k.qoff, k.koff, st))

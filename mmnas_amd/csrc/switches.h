@@ -60,7 +60,8 @@ struct Switch {
   X(gemm_ln_minm, "MMNAS_GEMM_LN_MINM", 2048, int, once, "fewest rows for the row-panel kernel (read together with MMNAS_GEMM_LN)") \
   X(gemm_ln_maxk, "MMNAS_GEMM_LN_MAXK", 256, int, once, "largest K for the row-panel kernel (read together with MMNAS_GEMM_LN)") \
   /* attention.hip, attention_bwd16.hip */ \
-  X(mha_nw, "MMNAS_MHA_NW", 4, int, every_call, "2: attention cores never use 4-wave workgroups (4-wave groups measured 7-15 % faster)") \
+  X(mha_nw, "MMNAS_MHA_NW", 4, int, every_call, "2: attention cores never use 4-wave workgroups (4-wave groups measured 7-15 % faster; the streaming forward always runs four)") \
+  X(mha_stream_mink, "MMNAS_MHA_STREAM_MINK", 257, int, every_call, "fewest keys at which the attention forward streams the keys in blocks of 128 (1..257; more than 256 keys always stream; dense rows only)") \
   X(mha_pair, "MMNAS_MHA_PAIR", 1, bool, once, "0: two attention cores of one geometry as two launches (mixed chain)") \
   X(mha_bwd_fused, "MMNAS_MHA_BWD_FUSED", 1, bool, once, "0: the attention backward as separate dQ and dK / dV kernels (dense rows only)") \
   X(mha_fwd_b16, "MMNAS_MHA_FWD_B16", 1, bool, once, "0: attention forward (d_h = 64, 65..128 keys) on the fp32 MFMA kernels instead of split-bf16 operands (profiles/r06_attention_b16_ab.txt)") \
