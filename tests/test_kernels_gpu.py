@@ -1117,6 +1117,50 @@ def test_lstm_vs_torch_fp64(B, T, E, H):
         del junk
 
 
+@pytest.mark.parametrize('T,B,E,H', [(2, 4, 32, 32), (5, 3, 20, 64)])
+def test_lstm_step_entry_points_vs_torch_fp64(T, B, E, H):
+    """The per-step LSTM entry points (mmnas_lstm_fwd / mmnas_lstm_bwd: one launch per time step on the GEMM kernel's
+    "LSTM time steps" rows) against torch.nn.LSTM in float64, with the layouts of include/mmnas_hip.h: time-major buffers,
+    gate columns interleaved (row / column 4j+g = gate g of unit j), bias = b_ih + b_hh, slice 0 of Hall / Call, slice T of DG
+    and dc zeroed by the caller.  The gradient of the pre-activations (DG) has no counterpart among nn.LSTM's outputs, so the
+    reference gets 4H extra input columns u_t = 0 with an identity block in W_ih: d loss / d u_t is DG[t].  Checked: the output
+    sequence, DG, and dW_ih / dW_hh formed from the kernel's DG (with x and the kernel's Hall) by plain torch products."""
+    L = _lib()
+    lib = L.lib()
+    assert lib.mmnas_lstm_supported(E, H)
+    torch.manual_seed(T + B + E + H)
+    ref = torch.nn.LSTM(input_size=E + 4 * H, hidden_size=H, num_layers=1, batch_first=True).double()
+    with torch.no_grad():
+        ref.weight_ih_l0[:, E:] = torch.eye(4 * H, dtype=torch.float64)
+    x = torch.randn(B, T, E, dtype=torch.float64)
+    u = torch.zeros(B, T, 4 * H, dtype=torch.float64, requires_grad=True)
+    go = torch.randn(B, T, H, dtype=torch.float64)
+    y = ref(torch.cat((x, u), dim=2))[0]
+    y.backward(go)
+    perm = (torch.arange(4)[None, :] * H + torch.arange(H)[:, None]).reshape(-1)      # perm[4j+g] = g H + j
+    Wih = ref.weight_ih_l0.detach()[perm, :E]
+    Whh = ref.weight_hh_l0.detach()[perm]
+    bias = (ref.bias_ih_l0 + ref.bias_hh_l0).detach()[perm]
+    z = lambda *s: torch.zeros(*s, device=DEV)
+    x_tm = g(x.transpose(0, 1).float())
+    Wih_d, Whh_d, bias_d = g(Wih.float()), g(Whh.float()), g(bias.float())
+    xp, Hall, Call, Gall, out = z(T, B, 4 * H), z(T + 1, B, H), z(T + 1, B, H), z(T, B, 4 * H), z(B, T, H)
+    L.check(lib.mmnas_lstm_fwd(*[L.fptr(t) for t in (x_tm, Wih_d, Whh_d, bias_d, xp, Hall, Call, Gall, out)], T, B, E, H, L.stream()))
+    DG, dc, scratch = z(T + 1, B, 4 * H), z(B, H), z(B, H)
+    L.check(lib.mmnas_lstm_bwd(*[L.fptr(t) for t in (g(go.float()), Whh_d, Call, Gall, DG, dc, scratch)], T, B, H, L.stream()))
+    torch.cuda.synchronize()
+    assert rel_err(out.cpu().numpy(), y.detach().numpy()) < 2e-5
+    assert rel_err(Hall[1:].cpu().numpy(), y.detach().transpose(0, 1).numpy()) < 2e-5      # h_t lands in slice t + 1
+    assert not Hall[0].any() and not Call[0].any() and not DG[T].any()
+    dg = DG[:T].cpu().double()
+    assert rel_err(dg.numpy(), u.grad.transpose(0, 1)[:, :, perm].numpy()) < 1e-4
+    dg2 = dg.reshape(T * B, 4 * H)
+    dWih = dg2.t() @ x.transpose(0, 1).reshape(T * B, E)
+    dWhh = dg2.t() @ Hall[:T].cpu().double().reshape(T * B, H)
+    assert rel_err(dWih.numpy(), ref.weight_ih_l0.grad[perm, :E].numpy()) < 1e-4
+    assert rel_err(dWhh.numpy(), ref.weight_hh_l0.grad[perm].numpy()) < 1e-4
+
+
 def test_embedding_backward_adds_rows_into_the_gradient():
     """ops.embedding: forward = nn.Embedding; backward adds dy rows into the weight gradient (duplicates accumulate),
     with and without a gradient sink (flat gradient buffer)."""
