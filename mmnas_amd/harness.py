@@ -17,6 +17,9 @@ implementation:
     net_optim='sgd' is the scripts' other NET_OPTIM branch (search_vqa.py:122-131,175-177,228-244,261): optim.FlatSGD +
     optim.CosineSchedule stepped by begin_epoch(); pinned by tests/golden/traj_sgd.npz (tests/test_sgd_gpu.py).
   * itm_triplet_step -- train_itm.py:380-391: three forwards (positive, negative caption, negative image), BCE_Loss.
+  * triplet_batch / BatchedTriplet -- the triplet steps of search_itm.py:381-447 for SearchLoop: the three forwards as one batch
+    of 3B samples, the three-argument loss over the three thirds of its scores.  Pinned against the reference's three forwards by
+    tests/golden/itm_search_traj.npz (tests/test_itm_search_gpu.py).
   * BCE_Loss -- mmnas/utils/itm_loss.py:4-24.  vgd_loss -- train_vgd.py:316-333.
 """
 import torch
@@ -92,6 +95,42 @@ def itm_triplet_step(net, loss_fn, pos, neg, reducer=None, optim=None):
     if optim is not None:
         optim.step()
     return loss
+
+
+def triplet_batch(pos, neg):
+    """The three forwards of an ITM triplet step (search_itm.py:373-375,385-387) as ONE batch of 3B samples
+    [pos; negc; negi]: the image fields (frcn, bbox, rel_img) come from (pos, pos, neg), the caption fields (cap_ix, rel_cap)
+    from (pos, neg, pos).  `pos` / `neg` are the 5-tuples of the matching pairs and of the mined negatives."""
+    def cat(i, a, b, c):
+        if a[i] is None:
+            return None
+        return torch.cat((a[i], b[i], c[i]), 0)
+    return (cat(0, pos, pos, neg), cat(1, pos, pos, neg), cat(2, pos, pos, neg), cat(3, pos, neg, pos), cat(4, pos, neg, pos))
+
+
+class BatchedTriplet(nn.Module):
+    """A three-argument ITM loss (BCE_Loss, Margin_Loss, losses.TripletBCELoss, ...) behind the (prediction, target) signature
+    of SearchLoop / TrainLoop: forward(scores, target) = loss_fn(scores[:B], scores[B:2B], scores[2B:]) for the [3B] scores of
+    a triplet_batch; the target is ignored.  fused_loss() and losses.fused() hand it back unchanged (wrap the fused loss
+    instead: BatchedTriplet(losses.fused(BCE_Loss(cfg)))).
+
+        loop = SearchLoop(net, loss_fn=BatchedTriplet(BCE_Loss(cfg)), arch_mode=...)
+        loop.weight_step(triplet_batch(pos, neg), None)      # search_itm.py:381-406
+        loop.arch_step(triplet_batch(epos, eneg), None)      # search_itm.py:408-447
+
+    One forward over 3B samples is, sample by sample, the arithmetic of the script's three forwards under the one sampled
+    architecture, with a third of the launches.  Dropout masks are drawn per sample of the one batch: the same distribution as
+    the three forwards', not the same draws."""
+
+    def __init__(self, loss_fn):
+        super().__init__()
+        self.loss_fn = loss_fn
+
+    def forward(self, scores, target=None):
+        if scores.shape[0] % 3:
+            raise ValueError('BatchedTriplet: %d scores are not the 3B of a triplet_batch' % scores.shape[0])
+        B = scores.shape[0] // 3
+        return self.loss_fn(scores[:B], scores[B:2 * B], scores[2 * B:])
 
 
 def hard_negative_indices(scores, neg_idx, hard_size):

@@ -26,6 +26,14 @@ distinct; recall_at_k reports how many queries a tie touched.  NaN scores raise.
 
 Batch invariance: captions and images are encoded, and pairs are scored, in batches of a fixed size (the last one padded
 by repeating its last row), so an entry of the score matrix does not depend on how the work was chunked or sharded.
+
+The search supernet (search_itm.py).  SupernetItmScorer scores an ITM Net_Search under the architecture that is installed when
+a method is called -- the sampled one of the mining pass (search_itm.py:267-348, MixedOp.MODE None, between
+unused_modules_off() and unused_modules_back()) or the chosen one of the evaluation (set_chosen_op_active()).  It is ItmScorer
+with each MixedOp standing for its active candidate: the same planner, the same kernels on the pair side.  The architecture is
+part of a cache: the scorer plans again when the installed indices changed, and refuses caches made under another architecture.
+mine_hard_negatives() is one mining pass over a scorer's caches for either anchor side, gather_mined() the script's all_gather,
+reordering and trim (search_itm.py:296-305).  The triplet steps of the search loop are harness.triplet_batch / BatchedTriplet.
 """
 import contextlib
 import ctypes as C
@@ -35,10 +43,13 @@ import torch
 
 from . import _lib as L
 from . import ops
+from . import switches
 from .model import modules as M
 from .model import nets
+from .model.mixed import MixedOp
 
-__all__ = ['ItmScorer', 'CaptionCache', 'ImageCache', 'recall_at_k', 'rank_matrix', 'hard_negative_indices', 'topk_positions']
+__all__ = ['ItmScorer', 'SupernetItmScorer', 'CaptionCache', 'ImageCache', 'recall_at_k', 'rank_matrix', 'hard_negative_indices',
+           'topk_positions', 'mine_hard_negatives', 'gather_mined', 'interleave_ranks']
 
 # decoder operators that never read `pre` (the language state): they run on the image side before the first guided operator
 # and per pair behind it
@@ -50,7 +61,9 @@ MAX_KEYS = 64   # the indexed attention core is the <= 64-key forward
 class CaptionCache:
     """Caption side of Net_Full for Nc captions.  x_mask [Nc,1,1,Sx] bool; mask8 [Nc,Sx] uint8 (the core's key mask);
     xflat [Nc, ATTFLAT_OUT] = attflat_x output; kv [Nc*Sx, ld]: the K / V of every guided operator, operator g's K in columns
-    kv_cols[g][0] .. + di_g, its V in kv_cols[g][1] .. + di_g."""
+    kv_cols[g][0] .. + di_g, its V in kv_cols[g][1] .. + di_g (kv is None when the decoder holds no guided operator).
+    arch: the architecture the cache was computed under (SupernetItmScorer.arch); None for a fixed network's."""
+    arch = None
 
     def __init__(self, x_mask, xflat, kv, kv_cols):
         self.x_mask, self.xflat, self.kv, self.kv_cols = x_mask, xflat, kv, kv_cols
@@ -63,7 +76,8 @@ class CaptionCache:
 
 class ImageCache:
     """Image side of Net_Full for Ni images: y_mask [Ni,1,1,Sy] bool, rel [Ni,Sy,Sy,4] the raw relation tensor, state
-    [Ni,Sy,HSIZE] the decoder state after the image-only prefix nodes."""
+    [Ni,Sy,HSIZE] the decoder state after the image-only prefix nodes.  arch: as CaptionCache's."""
+    arch = None
 
     def __init__(self, y_mask, rel, state):
         self.y_mask, self.rel, self.state = y_mask, rel, state
@@ -73,7 +87,9 @@ class ImageCache:
         return self.n
 
     def rows(self, start, end):
-        return ImageCache(self.y_mask[start:end], self.rel[start:end], self.state[start:end])
+        out = ImageCache(self.y_mask[start:end], self.rel[start:end], self.state[start:end])
+        out.arch = self.arch
+        return out
 
 
 def _pad_rows(t, n):
@@ -110,19 +126,28 @@ class ItmScorer:
             raise ValueError('ItmScorer: pair_batch and encode_batch must be positive')
         self.net = net
         self.pair_batch, self.encode_batch = int(pair_batch), int(encode_batch)
+        self._plan()
+
+    def _node_op(self, ci, ni, node):
+        """The one operator decoder cell ci's node ni stands for."""
+        if len(node) != 1:
+            raise ValueError('%s: decoder cell %d node %d holds %d operators; the scorer needs single-operator '
+                             'nodes' % (type(self).__name__, ci, ni, len(node)))
+        return node[0]
+
+    def _plan(self):
+        """Split the decoder into prefix_nodes / guided_ops / pair_nodes (class docstring)."""
+        name = type(self).__name__
         self.prefix_nodes, self.guided_ops, self.pair_nodes = [], [], []
         self._steps = []   # pair side in order: ('guided', op, g) / ('op', op)
         self._prefix = []
         seen_guided = False
-        for ci, cell in enumerate(net.backnone.cells_dec):
+        for ci, cell in enumerate(self.net.backnone.cells_dec):
             for ni, node in enumerate(cell.dag):
-                if len(node) != 1:
-                    raise ValueError('ItmScorer: decoder cell %d node %d holds %d operators; the scorer needs single-operator '
-                                     'nodes' % (ci, ni, len(node)))
-                op = node[0]
+                op = self._node_op(ci, ni, node)
                 if isinstance(op, M.UniimgAtt):
-                    raise ValueError('ItmScorer: decoder cell %d node %d is UniimgAtt, whose keys and values are cat(x, pre) -- '
-                                     'only GuidedAtt may read pre' % (ci, ni))
+                    raise ValueError('%s: decoder cell %d node %d is UniimgAtt, whose keys and values are cat(x, pre) -- '
+                                     'only GuidedAtt may read pre' % (name, ci, ni))
                 if type(op) is M.GuidedAtt:
                     seen_guided = True
                     self._steps.append(('guided', op, len(self.guided_ops)))
@@ -135,8 +160,8 @@ class ItmScorer:
                         self._prefix.append(op)
                         self.prefix_nodes.append((ci, ni))
                 else:
-                    raise ValueError('ItmScorer: decoder cell %d node %d holds %s, which the scorer does not know to be '
-                                     'independent of pre' % (ci, ni, type(op).__name__))
+                    raise ValueError('%s: decoder cell %d node %d holds %s, which the scorer does not know to be '
+                                     'independent of pre' % (name, ci, ni, type(op).__name__))
 
     # ---- mode handling ---------------------------------------------------------------------------------------------------
     @contextlib.contextmanager
@@ -347,6 +372,111 @@ class ItmScorer:
         return out
 
 
+def _whole_tile_products():
+    """mmnas_gemm on whole output tiles only (its scheduling row MMNAS_GEMM_SK at 0) while the block runs, the previous setting
+    afterwards.  The automatic schedule cuts the K sum of a product with few output tiles and a long K into runs (stream-K): the
+    same rows then get other bits at M = 36 than at M = 9216 (measured: 1.9e-6 on values of 4 at K = 512).  Whole tiles sum K in
+    one order whatever M and whichever tile shape (measured bit-equal from M = 36 to M = 147456, 64^2 and 128^2 tiles), which
+    is what makes a score independent of pair_batch and encode_batch."""
+    return switches.gemm_schedule({'MMNAS_GEMM_SK': 0})
+
+
+class SupernetItmScorer(ItmScorer):
+    """ItmScorer for the ITM search supernet (mmnas.model.hygr_itm.Net_Search, or DistributedDataParallel of one): factored
+    scoring of the architecture that is INSTALLED when a method is called -- every node's active_index[0], as
+    reset_binary_gates() / set_sampled(plan) / set_chosen_op_active() left it.  The planner is ItmScorer's, each MixedOp standing
+    for its active candidate; the same rules hold (only GuidedAtt may read pre, UniimgAtt raises; `none` is an ordinary pre-free
+    operator).  With no guided operator active the whole decoder is image-only: the caption cache has no K / V block and the pair
+    side is attflat_y plus the pair head.
+
+    `arch` is the tuple of the active indices of all encoder and decoder nodes the current plan was made for.  Every public
+    call compares it with the net's installed indices (a tuple comparison, no device work) and plans again when they differ;
+    the caches carry the `arch` they were computed under, and scoring with caches of another architecture raises ValueError.
+    A node without active_index (nothing sampled yet) raises ValueError.
+
+    Calls run in eval mode under no_grad with MixedOp.MODE = None and restore the training flags and MODE afterwards; indices,
+    gates, alphas and .grad are not written.  Only active candidates are read, so the scorer works between
+    unused_modules_off() and unused_modules_back() (search_itm.py:271-348 mines in that state).
+
+    While a call runs the products are scheduled on whole output tiles (_whole_tile_products), so a score has the same bits
+    whatever pair_batch and encode_batch are -- not only however the work was chunked at one batch size."""
+
+    def __init__(self, net, pair_batch=1024, encode_batch=256):
+        if isinstance(net, torch.nn.parallel.DistributedDataParallel):
+            net = net.module
+        if not isinstance(net, nets.NetSearchBase) or net.TASK != 'itm':
+            raise ValueError('SupernetItmScorer: needs an ITM Net_Search, got %s%s' % (
+                type(net).__name__, " for task '%s'" % net.TASK if isinstance(net, nets.NetSearchBase) else ''))
+        if int(pair_batch) < 1 or int(encode_batch) < 1:
+            raise ValueError('SupernetItmScorer: pair_batch and encode_batch must be positive')
+        self.net = net
+        self.pair_batch, self.encode_batch = int(pair_batch), int(encode_batch)
+        self.arch = None
+        self._sync()
+
+    def _installed(self):
+        arch = []
+        for i, m in enumerate(self.net.redundant_modules):
+            if not m.active_index:
+                raise ValueError('SupernetItmScorer: node %d has no active_index -- no architecture was sampled '
+                                 '(reset_binary_gates / set_sampled / set_chosen_op_active)' % i)
+            arch.append(int(m.active_index[0]))
+        return tuple(arch)
+
+    def _sync(self):
+        arch = self._installed()
+        if arch != self.arch:
+            self.arch = None      # (a plan that raises leaves no stale plan behind)
+            self._plan()
+            self.arch = arch
+
+    def _node_op(self, ci, ni, node):
+        mop = super()._node_op(ci, ni, node)
+        op = mop.candidate_ops[mop.active_index[0]]
+        if op is None:
+            raise ValueError('SupernetItmScorer: decoder cell %d node %d: the active candidate %d was taken out by '
+                             'unused_modules_off() under another architecture' % (ci, ni, mop.active_index[0]))
+        return op
+
+    @contextlib.contextmanager
+    def _eval(self):
+        mode = MixedOp.MODE
+        MixedOp.MODE = None
+        try:
+            with _whole_tile_products(), super()._eval():
+                yield
+        finally:
+            MixedOp.MODE = mode
+
+    def _same_arch(self, *caches):
+        for c in caches:
+            if isinstance(c, (ImageCache, CaptionCache)) and c.arch != self.arch:
+                raise ValueError('SupernetItmScorer: the %s was computed under architecture %r, the net now holds %r -- encode '
+                                 'again after a re-sample' % (type(c).__name__, c.arch, self.arch))
+
+    def encode_captions(self, cap_ix, rel_cap=None):
+        self._sync()
+        out = super().encode_captions(cap_ix, rel_cap)
+        out.arch = self.arch
+        return out
+
+    def encode_images(self, frcn_feat, bbox_feat, rel_img):
+        self._sync()
+        out = super().encode_images(frcn_feat, bbox_feat, rel_img)
+        out.arch = self.arch
+        return out
+
+    def score_pairs(self, images, captions, img_idx, cap_idx, logits=False):
+        self._sync()
+        self._same_arch(images, captions)
+        return super().score_pairs(images, captions, img_idx, cap_idx, logits)
+
+    def score_matrix(self, images, captions, rows=None, caption_chunk=1000, out=None):
+        self._sync()
+        self._same_arch(images, captions)
+        return super().score_matrix(images, captions, rows, caption_chunk, out)
+
+
 # ---- ranks, recall, mining -------------------------------------------------------------------------------------------------
 def _rank_numpy(S, G):
     Ni, Nc = S.shape
@@ -438,3 +568,46 @@ def hard_negative_indices(scores, neg_idx, hard_size):
     top = topk_positions(scores, int(hard_size))
     rows = torch.arange(top.size(0), device=top.device).unsqueeze(1).expand_as(top)
     return neg_idx.to(scores.device)[rows, top]
+
+
+def mine_hard_negatives(scorer, images, captions, anchor_idx, cand_idx, hard_size, anchor='image'):
+    """One hard-negative mining pass as search_itm.py / train_itm.py run it: [N, hard_size] int64 dataset indices, row n the
+    `hard_size` highest-scoring candidates among cand_idx[n, :] for anchor anchor_idx[n].  anchor='image': the anchors are
+    images and the candidates captions (search_itm.py:278-294); anchor='caption': the anchors are captions and the candidates
+    images (search_itm.py:313-333).  `images` / `captions` are the scorer's caches over the whole dataset (an ItmScorer or a
+    SupernetItmScorer); anchor_idx [N] and cand_idx [N, NEG_RANDSIZE] index into them.  Scores come from score_pairs, the
+    selection from hard_negative_indices (equal scores by the lower candidate position)."""
+    if anchor not in ('image', 'caption'):
+        raise ValueError("mine_hard_negatives: anchor is 'image' or 'caption', got %r" % (anchor,))
+    cand_idx = torch.as_tensor(cand_idx).long()
+    anchor_idx = torch.as_tensor(anchor_idx).long().reshape(-1)
+    if cand_idx.dim() != 2 or cand_idx.shape[0] != anchor_idx.numel():
+        raise ValueError('mine_hard_negatives: cand_idx must be [N, NEG_RANDSIZE] for anchor_idx [N]; got %s and %s'
+                         % (tuple(cand_idx.shape), tuple(anchor_idx.shape)))
+    own = anchor_idx.to(cand_idx.device).repeat_interleave(cand_idx.shape[1])
+    other = cand_idx.reshape(-1)
+    if anchor == 'image':
+        scores = scorer.score_pairs(images, captions, own, other)
+    else:
+        scores = scorer.score_pairs(images, captions, other, own)
+    return hard_negative_indices(scores, cand_idx, hard_size)
+
+
+def interleave_ranks(parts):
+    """The per-rank mining results [n, hard_size] of a SubsetDistributedSampler's shards in dataset order: rank r's i-th row
+    lands at r + world * i (search_itm.py:300: cat(dim=1) of the unsqueezed results, viewed as [-1, hard_size])."""
+    hard = parts[0].shape[-1]
+    return torch.cat([p.unsqueeze(1) for p in parts], dim=1).view(-1, hard)
+
+
+def gather_mined(local, world, rest, group=None):
+    """search_itm.py:296-305: all_gather the ranks' mining results `local` [n, hard_size], put them in the sampler's order
+    (interleave_ranks) and drop the last `rest` rows (the sampler's padding, `sampler.rest_data_num`).  Returns a CPU tensor,
+    as the script hands it to the datasets.  world == 1, or no initialised process group: only the trim."""
+    import torch.distributed as dist
+    if int(world) > 1 and dist.is_available() and dist.is_initialized():
+        parts = [torch.zeros_like(local) for _ in range(int(world))]
+        dist.all_gather(parts, local.contiguous(), group=group)
+        local = interleave_ranks(parts)
+    local = local.cpu()
+    return local[:-int(rest)] if rest else local

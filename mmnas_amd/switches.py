@@ -15,6 +15,7 @@ the two by tools/switch_table.py).
 
 Flag.set installs an override that every later get() returns, whatever the policy, and returns the previous value.
 """
+import contextlib
 import os
 
 _PARSE = {
@@ -83,6 +84,32 @@ DP_EARLY_SCATTER = _flag('MMNAS_DP_EARLY_SCATTER', False, 'is1', 'every_call', "
 LIB_PATH = _flag('MMNAS_LIB_PATH', None, 'string', 'doc', 'path of the shared library to load instead of mmnas_amd/lib/libmmnas_hip.so (tuning builds; read when _lib.py is imported)')
 _flag('MMNAS_REFERENCE_ROOT', None, 'string', 'doc', "a checkout of the reference whose mmnas/ package is merged behind this repository's (mmnas/__init__.py)")
 _flag('MMNAS_PROF_DUMP', None, 'string', 'doc', 'file the native profiler appends one row per bracketed launch to (csrc/util.hip)')
+
+
+@contextlib.contextmanager
+def gemm_schedule(rows):
+    """The native library's GEMM scheduling rows (policy `reload` in csrc/switches.h) at the given values while the block runs --
+    gemm_schedule({'MMNAS_GEMM_SK': 0}): whole output tiles, no stream-K -- and as they were afterwards.  The library reads these
+    rows from the environment, so that is where the values go; mmnas_gemm_reload_tuning makes it read them again."""
+    from . import _lib as L
+    known = native()
+    for name in rows:
+        if name not in known:
+            raise ValueError('gemm_schedule: %s is not a row of the native switch table' % name)
+    saved = {}
+    try:
+        for name, v in rows.items():
+            saved[name] = os.environ.get(name)
+            os.environ[name] = str(int(v))
+        L.lib().mmnas_gemm_reload_tuning()
+        yield
+    finally:
+        for name, v in saved.items():
+            if v is None:
+                os.environ.pop(name, None)
+            else:
+                os.environ[name] = v
+        L.lib().mmnas_gemm_reload_tuning()
 
 
 def native():
