@@ -359,6 +359,28 @@ int mmnas_alpha_full_step_wd(float* prob, const float* gate_grad, float* m, floa
 int mmnas_alpha_two_step(float* prob, const float* gate_grad, float* m, float* v, float* prob_grad, int rows, int width,
                          const int* pair_host, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                          void* stream);
+/* The two updates above with the expected-cost term of a hardware-aware search (ProxylessNAS): cost [rows, width] holds one
+ * figure per candidate, 0 in the padding columns.  With p = softmax(alpha_r) over the WHOLE row, E_r = sum_j p_j cost[r, j]
+ * and E = sum_r E_r -- both from the alphas before the update -- the regulariser is
+ *   cost_form 0 ('linear'): R = cost_weight * (E - cost_ref) / cost_ref,  k = cost_weight / cost_ref
+ *   cost_form 1 ('log'):    R = cost_weight * log(E / cost_ref),          k = cost_weight / E   (E <= 0: R = 0, k = 0)
+ * and k p_j (cost[r, j] - E_r) is added to dalpha on every live column, in 'two' mode too (the pair gradient stays the softmax
+ * over the pair; Adam and the rescale of the pair follow as above).  prob_grad (nullable) receives task part + cost part, the
+ * weight decay comes after it.  stats (nullable; rows + 2 floats) receives E_r of every row, then E, then R.
+ * One launch of ONE 256-thread workgroup that walks the rows r, r + 256, ...: E is summed in a fixed order (no atomics: the
+ * same inputs give the same bits) and is known before any alpha moves.  'full': any rows >= 0; 'two': rows <= 128, else
+ * MMNAS_E_SHAPE.  Both read beta1 / beta2 as the decimals the caller wrote and form 1 - beta and the bias corrections in
+ * double on the host, as mmnas_alpha_two_step does (mmnas_alpha_full_step forms them in float: its exp_avg_sq differs from
+ * this entry's by the factor 0.001 / (1 - 0.999f) at cost_weight = 0, its alphas do not).
+ * MMNAS_E_ARG, before any launch: a null pointer (stats and prob_grad excepted), cost_form outside 0 / 1, cost_ref not finite
+ * or <= 0, cost_weight negative or not finite, step < 1, width < 1 ('two': < 2), a bad pair. */
+int mmnas_alpha_full_step_cost(float* prob, const float* gate_grad, float* m, float* v, float* prob_grad, const float* cost,
+                               float* stats, int rows, int width, float lr, float beta1, float beta2, float eps,
+                               float weight_decay, float cost_weight, float cost_ref, int cost_form, int step, void* stream);
+int mmnas_alpha_two_step_cost(float* prob, const float* gate_grad, float* m, float* v, float* prob_grad, const float* cost,
+                              float* stats, int rows, int width, const int* pair_host, float lr, float beta1, float beta2,
+                              float eps, float weight_decay, float cost_weight, float cost_ref, int cost_form, int step,
+                              void* stream);
 
 /* nn.Embedding backward (hygr_vqa.py:85,105; aten embedding_dense_backward): dW[idx[t], :] += dy[t, :] for the n_tok
  * int64 token indices -- straight into the (already zeroed or accumulating) gradient buffer instead of a dense

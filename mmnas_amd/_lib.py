@@ -199,6 +199,8 @@ SYMBOLS = {
     'mmnas_alpha_full_step': (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _f, _f, _f, _f, _i, _fp]),
     'mmnas_alpha_full_step_wd': (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _f, _f, _f, _f, _f, _i, _fp]),
     'mmnas_alpha_two_step': (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, C.POINTER(C.c_int), _f, _f, _f, _f, _f, _i, _fp]),
+    'mmnas_alpha_full_step_cost': (_i, [_fp] * 7 + [_i, _i, _f, _f, _f, _f, _f, _f, _f, _i, _i, _fp]),
+    'mmnas_alpha_two_step_cost': (_i, [_fp] * 7 + [_i, _i, C.POINTER(C.c_int), _f, _f, _f, _f, _f, _f, _f, _i, _i, _fp]),
     'mmnas_embedding_bwd': (_i, [_fp, _fp, _fp, C.c_long, _i, C.c_long, _fp]),
     'mmnas_node_mix_fwd': (_i, [_fp, _fp, _fp, _i, _fp, _fp, _i, _i, _f, _fp]),
     'mmnas_node_mix_bwd': (_i, [_fp, _fp, _fp, _i, _fp, _fp, _fp, _i, _fp, _fp, _i, _i, _f, _fp]),

@@ -365,12 +365,64 @@ __global__ void __launch_bounds__(256) node_mix_bwd_kernel(NodeMixArgs p, const 
   }
 }
 
-// one thread per node (row): 'full'-mode architecture gradient + Adam
-__global__ void alpha_full_step_kernel(float* __restrict__ prob, const float* __restrict__ gate_grad, float* __restrict__ m,
-                                       float* __restrict__ v, float* __restrict__ prob_grad, int rows, int width, float lr,
-                                       float b1, float b2, float eps, float c1, float c2s, float wd) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= rows) return;
+// The expected-cost term of the hardware-aware search (ProxylessNAS, section 3.3): with p = softmax(alpha_r) over the whole
+// row, E_r = sum_j p_j cost[r, j] and E = sum_r E_r, the regulariser R is weight * (E - ref) / ref ('linear', k = weight / ref)
+// or weight * log(E / ref) ('log', k = weight / E), and dR/dalpha[r, j] = k p_j (cost[r, j] - E_r) on every live column.
+struct AlphaCost {
+  const float* cost;   // [rows, width], 0 in the padding columns
+  float* stats;        // nullable: E_r per row, then E, then R
+  float weight, ref;
+  int form;            // 0 linear, 1 log
+};
+
+// E_r of one row (padding columns hold -inf: exp = 0)
+__device__ __forceinline__ float alpha_row_expected_cost(const float* __restrict__ a, const float* __restrict__ c, int width) {
+  float mx = -INFINITY;
+  for (int i = 0; i < width; ++i) mx = fmaxf(mx, a[i]);
+  float den = 0.f;
+  for (int i = 0; i < width; ++i) den += expf(a[i] - mx);
+  float e = 0.f;
+  for (int i = 0; i < width; ++i) e += (expf(a[i] - mx) / den) * c[i];
+  return e;
+}
+
+// Pass 1 of the cost kernels, one 256-thread workgroup: thread t takes the rows t, t + 256, ... in that order, the waves' sums
+// (lane permutations) meet in LDS and every thread adds the four in one fixed order -- no atomics, the same bits on every call.
+// Returns k (see AlphaCost); thread 0 stores E and R.  The barrier inside also separates every read of the old alphas (the
+// total is needed before any alpha moves: 'log' divides by it) from the first store of pass 2.
+__device__ __forceinline__ float alpha_cost_scale(const float* __restrict__ prob, int rows, int width, const AlphaCost& ac) {
+  __shared__ float red[4];
+  float part = 0.f;
+  for (int r = threadIdx.x; r < rows; r += 256) {
+    const float e = alpha_row_expected_cost(prob + (size_t)r * width, ac.cost + (size_t)r * width, width);
+    if (ac.stats) ac.stats[r] = e;
+    part += e;
+  }
+  part = wave_sum(part);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
+  __syncthreads();
+  const float E = (red[0] + red[1]) + (red[2] + red[3]);
+  float k = 0.f, R = 0.f;
+  if (ac.form == 0) {
+    k = ac.weight / ac.ref;
+    R = ac.weight * (E - ac.ref) / ac.ref;
+  } else if (E > 0.f) {                                     // (E <= 0: every positive-cost candidate underflowed -- no term)
+    k = ac.weight / E;
+    R = ac.weight * logf(E / ac.ref);
+  }
+  if (ac.stats && threadIdx.x == 0) {
+    ac.stats[rows] = E;
+    ac.stats[rows + 1] = R;
+  }
+  return k;
+}
+
+// one node (row) of the 'full'-mode architecture gradient + Adam; COST: plus k p_i (cost_i - E_r)
+template <bool COST>
+__device__ __forceinline__ void alpha_full_row(float* __restrict__ prob, const float* __restrict__ gate_grad, float* __restrict__ m,
+                                               float* __restrict__ v, float* __restrict__ prob_grad, int r, int width, float lr,
+                                               float b1, float b2, float omb1, float omb2, float eps, float c1, float c2s, float wd,
+                                               const float* __restrict__ cost, float k) {
   float* a = prob + (size_t)r * width;
   const float* g = gate_grad + (size_t)r * width;
   float mx = -INFINITY;
@@ -379,18 +431,42 @@ __global__ void alpha_full_step_kernel(float* __restrict__ prob, const float* __
   for (int i = 0; i < width; ++i) den += expf(a[i] - mx);   // padding columns hold -inf: exp = 0
   float dot = 0.f;
   for (int i = 0; i < width; ++i) dot += g[i] * (expf(a[i] - mx) / den);
+  float er = 0.f;
+  if (COST)
+    for (int i = 0; i < width; ++i) er += (expf(a[i] - mx) / den) * cost[(size_t)r * width + i];
   for (int i = 0; i < width; ++i) {
     const float p = expf(a[i] - mx) / den;
     float grad = p * (g[i] - dot);                          // sum_j g_j p_j (delta_ij - p_i), mixed.py:194-198
+    if (COST) grad += k * p * (cost[(size_t)r * width + i] - er);
     if (prob_grad) prob_grad[(size_t)r * width + i] = grad;
     if (p == 0.f && !(a[i] > -INFINITY)) continue;          // padding column: stays -inf
     if (wd != 0.f) grad += wd * a[i];                       // torch Adam's weight_decay (ALPHA_WEIGHT_DECAY): p.grad itself stays as it is
     const size_t o = (size_t)r * width + i;
-    const float mi = b1 * m[o] + (1.f - b1) * grad;
-    const float vi = b2 * v[o] + (1.f - b2) * grad * grad;
+    const float mi = b1 * m[o] + omb1 * grad;
+    const float vi = b2 * v[o] + omb2 * grad * grad;
     m[o] = mi; v[o] = vi;
     a[i] -= (lr / c1) * mi / (sqrtf(vi) / c2s + eps);
   }
+}
+
+// one thread per node (row): 'full'-mode architecture gradient + Adam
+__global__ void alpha_full_step_kernel(float* __restrict__ prob, const float* __restrict__ gate_grad, float* __restrict__ m,
+                                       float* __restrict__ v, float* __restrict__ prob_grad, int rows, int width, float lr,
+                                       float b1, float b2, float eps, float c1, float c2s, float wd) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= rows) return;
+  alpha_full_row<false>(prob, gate_grad, m, v, prob_grad, r, width, lr, b1, b2, 1.f - b1, 1.f - b2, eps, c1, c2s, wd, nullptr, 0.f);
+}
+
+// the same with the expected-cost term: ONE workgroup of 256 threads walks the rows (alpha_cost_scale says why)
+__global__ __launch_bounds__(256) void alpha_full_step_cost_kernel(float* __restrict__ prob, const float* __restrict__ gate_grad,
+                                                                   float* __restrict__ m, float* __restrict__ v,
+                                                                   float* __restrict__ prob_grad, int rows, int width, float lr,
+                                                                   float b1, float b2, float omb1, float omb2, float eps, float c1,
+                                                                   float c2s, float wd, AlphaCost ac) {
+  const float k = alpha_cost_scale(prob, rows, width, ac);
+  for (int r = threadIdx.x; r < rows; r += 256)
+    alpha_full_row<true>(prob, gate_grad, m, v, prob_grad, r, width, lr, b1, b2, omb1, omb2, eps, c1, c2s, wd, ac.cost, k);
 }
 
 // one thread per node (row): 'two'-mode architecture gradient over the sampled pair + Adam over the row + the pair's
@@ -398,13 +474,13 @@ __global__ void alpha_full_step_kernel(float* __restrict__ prob, const float* __
 constexpr int ALPHA_TWO_MAX_ROWS = 128;                    // mmnas_onehot_rows' limit: 1 KB of kernel arguments
 struct AlphaPairArgs { int ij[ALPHA_TWO_MAX_ROWS * 2]; };   // (active, inactive) per row
 
-__global__ void alpha_two_step_kernel(float* __restrict__ prob, const float* __restrict__ gate_grad, float* __restrict__ m,
-                                      float* __restrict__ v, float* __restrict__ prob_grad, int rows, int width, float lr,
-                                      float b1, float b2, float omb1, float omb2, float eps, float c1, float c2s, float wd,
-                                      AlphaPairArgs pa) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= rows) return;
-  const int pi = pa.ij[2 * r], pj = pa.ij[2 * r + 1];       // (checked on the host: 0 <= pi != pj < width)
+// COST: k p_i (cost_i - E_r), p the softmax over the WHOLE row, joins the pair gradient on every live column (the regulariser
+// reaches all paths, the binary-gate gradient the sampled two)
+template <bool COST>
+__device__ __forceinline__ void alpha_two_row(float* __restrict__ prob, const float* __restrict__ gate_grad, float* __restrict__ m,
+                                              float* __restrict__ v, float* __restrict__ prob_grad, int r, int width, float lr,
+                                              float b1, float b2, float omb1, float omb2, float eps, float c1, float c2s, float wd,
+                                              int pi, int pj, const float* __restrict__ cost, float k) {
   float* a = prob + (size_t)r * width;
   const float* g = gate_grad + (size_t)r * width;
   const float oi = a[pi], oj = a[pj];                       // the pair's logits before Adam
@@ -415,11 +491,18 @@ __global__ void alpha_two_step_kernel(float* __restrict__ prob, const float* __r
   const float gpi = g[pi] * si, gpj = g[pj] * sj;
   const float dot = gpi + gpj;
   const float gi = gpi - si * dot, gj = gpj - sj * dot;     // sum_k g_k p_k (delta_ik - p_i) over the pair (mixed.py:182-186)
+  float rmx = -INFINITY, rden = 0.f, er = 0.f;
+  if (COST) {
+    for (int i = 0; i < width; ++i) rmx = fmaxf(rmx, a[i]);
+    for (int i = 0; i < width; ++i) rden += expf(a[i] - rmx);
+    for (int i = 0; i < width; ++i) er += (expf(a[i] - rmx) / rden) * cost[(size_t)r * width + i];
+  }
   for (int i = 0; i < width; ++i) {
     float grad = i == pi ? gi : (i == pj ? gj : 0.f);
     const size_t o = (size_t)r * width + i;
-    if (prob_grad) prob_grad[o] = grad;
     const float ai = a[i];
+    if (COST) grad += k * (expf(ai - rmx) / rden) * (cost[o] - er);
+    if (prob_grad) prob_grad[o] = grad;
     if (!(ai > -INFINITY)) continue;                        // padding column: stays -inf, its moments untouched
     if (wd != 0.f) grad += wd * ai;                         // torch Adam's weight_decay: p.grad itself stays as it is
     const float mi = b1 * m[o] + omb1 * grad;               // omb = 1 - beta, formed on the host (see mmnas_alpha_two_step)
@@ -436,6 +519,28 @@ __global__ void alpha_two_step_kernel(float* __restrict__ prob, const float* __r
   const double off = ((double)nmx - (double)mx) + log(nden / oden);
   a[pi] = (float)((double)ni - off);
   a[pj] = (float)((double)nj - off);
+}
+
+__global__ void alpha_two_step_kernel(float* __restrict__ prob, const float* __restrict__ gate_grad, float* __restrict__ m,
+                                      float* __restrict__ v, float* __restrict__ prob_grad, int rows, int width, float lr,
+                                      float b1, float b2, float omb1, float omb2, float eps, float c1, float c2s, float wd,
+                                      AlphaPairArgs pa) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= rows) return;
+  alpha_two_row<false>(prob, gate_grad, m, v, prob_grad, r, width, lr, b1, b2, omb1, omb2, eps, c1, c2s, wd, pa.ij[2 * r],
+                       pa.ij[2 * r + 1], nullptr, 0.f);   // (checked on the host: 0 <= pi != pj < width)
+}
+
+// the same with the expected-cost term: one workgroup of 256 threads (rows <= ALPHA_TWO_MAX_ROWS: a single pass each)
+__global__ __launch_bounds__(256) void alpha_two_step_cost_kernel(float* __restrict__ prob, const float* __restrict__ gate_grad,
+                                                                  float* __restrict__ m, float* __restrict__ v,
+                                                                  float* __restrict__ prob_grad, int rows, int width, float lr,
+                                                                  float b1, float b2, float omb1, float omb2, float eps, float c1,
+                                                                  float c2s, float wd, AlphaPairArgs pa, AlphaCost ac) {
+  const float k = alpha_cost_scale(prob, rows, width, ac);
+  for (int r = threadIdx.x; r < rows; r += 256)
+    alpha_two_row<true>(prob, gate_grad, m, v, prob_grad, r, width, lr, b1, b2, omb1, omb2, eps, c1, c2s, wd, pa.ij[2 * r],
+                        pa.ij[2 * r + 1], ac.cost, k);
 }
 
 }  // namespace mmnas
@@ -534,6 +639,61 @@ extern "C" int mmnas_alpha_two_step(float* prob, const float* gate_grad, float* 
   MMNAS_LAUNCH(alpha_two_step_kernel, dim3(cdiv(rows, 64)), dim3(64), 0, (hipStream_t)stream, prob, gate_grad, m, v, prob_grad,
                rows, width, lr, beta1, beta2, (float)(1.0 - b1), (float)(1.0 - b2), eps, c1, c2s, weight_decay, pa);
   return check_launch("alpha_two_step");
+}
+
+// The cost entries: what both check before anything else; the coefficients as mmnas_alpha_two_step forms them (in 'full' too:
+// float(1 - 0.999f) is 1.3e-5 away from 0.001, more than the entries' float64 checks allow exp_avg_sq).
+static int alpha_cost_args(const char* who, const float* prob, const float* gate_grad, const float* m, const float* v,
+                           const float* cost, int width, int min_width, float cost_weight, float cost_ref, int cost_form, int step) {
+  MMNAS_REQUIRE(step >= 1 && width >= min_width, MMNAS_E_ARG, "%s: step=%d (>= 1) width=%d (>= %d)", who, step, width, min_width);
+  MMNAS_REQUIRE(cost_form == 0 || cost_form == 1, MMNAS_E_ARG, "%s: cost_form=%d (0 linear, 1 log)", who, cost_form);
+  MMNAS_REQUIRE(std::isfinite(cost_ref) && cost_ref > 0.f, MMNAS_E_ARG, "%s: cost_ref=%g must be finite and positive", who, (double)cost_ref);
+  MMNAS_REQUIRE(std::isfinite(cost_weight) && cost_weight >= 0.f, MMNAS_E_ARG, "%s: cost_weight=%g must be finite and not negative", who,
+                (double)cost_weight);
+  MMNAS_REQUIRE(prob && gate_grad && m && v && cost, MMNAS_E_ARG, "%s: null pointer", who);
+  return MMNAS_OK;
+}
+
+extern "C" int mmnas_alpha_full_step_cost(float* prob, const float* gate_grad, float* m, float* v, float* prob_grad,
+                                          const float* cost, float* stats, int rows, int width, float lr, float beta1, float beta2,
+                                          float eps, float weight_decay, float cost_weight, float cost_ref, int cost_form, int step,
+                                          void* stream) {
+  MMNAS_REQUIRE(rows >= 0, MMNAS_E_ARG, "mmnas_alpha_full_step_cost: rows=%d", rows);
+  const int rc = alpha_cost_args("mmnas_alpha_full_step_cost", prob, gate_grad, m, v, cost, width, 1, cost_weight, cost_ref, cost_form, step);
+  if (rc != MMNAS_OK) return rc;
+  const double b1 = decimal_of(beta1), b2 = decimal_of(beta2);
+  const float c1 = (float)(1.0 - pow(b1, (double)step));
+  const float c2s = (float)sqrt(1.0 - pow(b2, (double)step));
+  const AlphaCost ac{cost, stats, cost_weight, cost_ref, cost_form};
+  MMNAS_LAUNCH(alpha_full_step_cost_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, prob, gate_grad, m, v, prob_grad, rows, width,
+               lr, beta1, beta2, (float)(1.0 - b1), (float)(1.0 - b2), eps, c1, c2s, weight_decay, ac);
+  return check_launch("alpha_full_step_cost");
+}
+
+extern "C" int mmnas_alpha_two_step_cost(float* prob, const float* gate_grad, float* m, float* v, float* prob_grad,
+                                         const float* cost, float* stats, int rows, int width, const int* pair_host, float lr,
+                                         float beta1, float beta2, float eps, float weight_decay, float cost_weight, float cost_ref,
+                                         int cost_form, int step, void* stream) {
+  MMNAS_REQUIRE(rows >= 0 && rows <= ALPHA_TWO_MAX_ROWS, MMNAS_E_SHAPE, "mmnas_alpha_two_step_cost: rows=%d (0..%d)", rows, ALPHA_TWO_MAX_ROWS);
+  const int rc = alpha_cost_args("mmnas_alpha_two_step_cost", prob, gate_grad, m, v, cost, width, 2, cost_weight, cost_ref, cost_form, step);
+  if (rc != MMNAS_OK) return rc;
+  MMNAS_REQUIRE(pair_host, MMNAS_E_ARG, "mmnas_alpha_two_step_cost: null pointer");
+  AlphaPairArgs pa;
+  memset(&pa, 0, sizeof(pa));
+  for (int r = 0; r < rows; ++r) {
+    const int i = pair_host[2 * r], j = pair_host[2 * r + 1];
+    MMNAS_REQUIRE(i >= 0 && i < width && j >= 0 && j < width && i != j, MMNAS_E_ARG,
+                  "mmnas_alpha_two_step_cost: row %d: pair (%d, %d) must be two different columns of 0..%d", r, i, j, width - 1);
+    pa.ij[2 * r] = i;
+    pa.ij[2 * r + 1] = j;
+  }
+  const double b1 = decimal_of(beta1), b2 = decimal_of(beta2);
+  const float c1 = (float)(1.0 - pow(b1, (double)step));
+  const float c2s = (float)sqrt(1.0 - pow(b2, (double)step));
+  const AlphaCost ac{cost, stats, cost_weight, cost_ref, cost_form};
+  MMNAS_LAUNCH(alpha_two_step_cost_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, prob, gate_grad, m, v, prob_grad, rows, width,
+               lr, beta1, beta2, (float)(1.0 - b1), (float)(1.0 - b2), eps, c1, c2s, weight_decay, pa, ac);
+  return check_launch("alpha_two_step_cost");
 }
 
 

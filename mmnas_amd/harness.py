@@ -22,10 +22,13 @@ implementation:
     tests/golden/itm_search_traj.npz (tests/test_itm_search_gpu.py).
   * BCE_Loss -- mmnas/utils/itm_loss.py:4-24.  vgd_loss -- train_vgd.py:316-333.
 """
+import math
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import cost as cost_tables
 from . import dp, ops
 from .model.mixed import MixedOp
 from .optim import CosineSchedule, FlatAdam, FlatSGD, WarmupOptimizer
@@ -148,9 +151,13 @@ class ArchAdam:
     with Net_Search.set_arch_param_grad() for ALPHA_BINARY_MODE 'full': one kernel over the [n_nodes, width] blocks.
     mode='two': the same for ALPHA_BINARY_MODE 'two' -- set_arch_param_grad over each node's sampled pair, the Adam step and
     rescale_updated_arch_param (search_vqa.py:330-335, mixed.py:179-208) as one kernel (ops.alpha_two_step); the pairs are
-    read from the nodes' active_index / inactive_index when step() runs.  The checkpoint format is the same in both modes."""
+    read from the nodes' active_index / inactive_index when step() runs.  The checkpoint format is the same in both modes.
+    cost (a [nodes, width] block or a cost.CostTable) with cost_weight > 0: the expected-cost regulariser of a hardware-aware
+    search, 'linear' or 'log' around cost_ref (default: the expected cost under uniform alphas), joins the objective in the
+    same launch (ops.alpha_cost_step); `cost_stats` then holds E_r per node, E and R of the last update on the device."""
 
-    def __init__(self, net, lr=0.1, betas=(0.0, 0.999), eps=1e-8, weight_decay=0, mode='full'):
+    def __init__(self, net, lr=0.1, betas=(0.0, 0.999), eps=1e-8, weight_decay=0, mode='full', cost=None, cost_weight=0.0,
+                 cost_form='linear', cost_ref=None):
         if mode not in ('full', 'two'):
             raise ValueError("ArchAdam: mode is 'full' or 'two', got %r" % (mode,))
         self.mode = mode
@@ -160,6 +167,29 @@ class ArchAdam:
         self.m = torch.zeros_like(prob)
         self.v = torch.zeros_like(prob)
         self.steps = 0
+        # hardware-aware search: the expected-cost regulariser joins the objective inside the same launch
+        # (ops.alpha_cost_step).  Configuration, not state: nothing of it enters state_dict().  Without a table or with
+        # cost_weight == 0 step() is the update above, call for call.
+        self.cost = self.cost_stats = None
+        self.cost_weight, self.cost_form, self.cost_ref = float(cost_weight), cost_form, cost_ref
+        if cost is not None and self.cost_weight != 0.0:
+            if cost_form not in ops.COST_FORMS:
+                raise ValueError("ArchAdam: cost_form is 'linear' or 'log', got %r" % (cost_form,))
+            if not (math.isfinite(self.cost_weight) and self.cost_weight > 0):
+                raise ValueError('ArchAdam: cost_weight must be finite and not negative, got %r' % (cost_weight,))
+            n_choices = [m.n_choices for m in net.redundant_modules]
+            block = cost.for_net(net, cost_form) if isinstance(cost, cost_tables.CostTable) else cost
+            if tuple(block.shape) != tuple(prob.shape):
+                raise ValueError('ArchAdam: the cost block is %s, the alpha block %s' % (tuple(block.shape), tuple(prob.shape)))
+            block = cost_tables.check_block(block.detach().to('cpu', torch.float32), n_choices, cost_form)
+            if cost_ref is None:
+                self.cost_ref = cost_tables.uniform_expected(block, n_choices)
+            self.cost_ref = float(self.cost_ref)
+            if not (math.isfinite(self.cost_ref) and self.cost_ref > 0):
+                raise ValueError('ArchAdam: cost_ref must be finite and positive, got %r (the default is the expected cost under '
+                                 'uniform alphas: pass one for a table of zeros)' % (self.cost_ref,))
+            self.cost = block.to(prob.device).contiguous()
+            self.cost_stats = torch.zeros(prob.shape[0] + 2, device=prob.device)      # E_r per node, E, R of the last update
 
     def _sampled_pairs(self):
         pairs = []
@@ -185,7 +215,11 @@ class ArchAdam:
             if g is not None and g.data_ptr() != gg[i].data_ptr():
                 gg[i, :m.n_choices].copy_(g)
         self.steps += 1
-        if pairs is not None:
+        if self.cost is not None:
+            ops.alpha_cost_step(prob, gg, self.m, self.v, pg, self.cost, self.lr, self.betas, self.eps, self.steps, self.weight_decay,
+                                cost_weight=self.cost_weight, cost_ref=self.cost_ref, cost_form=self.cost_form, pairs=pairs,
+                                stats=self.cost_stats)
+        elif pairs is not None:
             ops.alpha_two_step(prob, gg, self.m, self.v, pg, pairs, self.lr, self.betas, self.eps, self.steps, self.weight_decay)
         else:
             ops.alpha_full_step(prob, gg, self.m, self.v, pg, self.lr, self.betas, self.eps, self.steps, self.weight_decay)
@@ -277,15 +311,20 @@ class SearchLoop:
     (search_vqa.py:261-262).  To resume, pass start_epoch=CKPT_EPOCH and load the checkpoint's 'net_optim' into
     `loop.net_optim` (search_vqa.py:226-231).  net_weight_decay / alpha_weight_decay: NET_WEIGHT_DECAY / ALPHA_WEIGHT_DECAY.
     fused_arch_update (arch_mode='two' only): the architecture update as ArchAdam(mode='two') instead of the per-node
-    statements around torch Adam; the checkpoints of the two are interchangeable."""
+    statements around torch Adam; the checkpoints of the two are interchangeable.
+    cost_table / cost_weight / cost_form / cost_ref: ArchAdam's expected-cost term ('two' carries it only under
+    fused_arch_update=True); without a table or with cost_weight 0 the architecture update is unchanged."""
 
     def __init__(self, net, loss_fn=None, net_lr=4e-4, net_betas=(0.9, 0.98), net_eps=1e-9, clip=1.0, epoch_steps=1000,
                  warmup=True, alpha_lr=0.1, alpha_betas=(0.0, 0.999), alpha_every=5, arch_mode='full', group=None,
                  absent_grads='zero', n_buckets=3, force_collectives=False, net_optim='wadam', net_momentum=0.9,
                  net_weight_decay=0.0, net_lr_min=0.0005, max_epoch=None, start_epoch=0, alpha_weight_decay=0.0,
-                 fused_arch_update=False):
+                 fused_arch_update=False, cost_table=None, cost_weight=0.0, cost_form='linear', cost_ref=None):
         if arch_mode not in ('full', 'two'):
             raise ValueError("ALPHA_BINARY_MODE is 'full' or 'two' (search_vqa.py:151), got %r" % (arch_mode,))
+        if cost_table is not None and arch_mode == 'two' and not fused_arch_update:
+            raise ValueError("cost_table with arch_mode='two' needs fused_arch_update=True: the per-node statements around torch "
+                             "Adam do not carry the expected-cost term")
         if net_optim not in ('wadam', 'sgd'):
             raise ValueError("NET_OPTIM is 'wadam' or 'sgd' (search_vqa.py:117-118), got %r" % (net_optim,))
         if net_optim == 'sgd' and max_epoch is None:
@@ -320,10 +359,11 @@ class SearchLoop:
         # fused_arch_update=True gives 'two' the same device-resident update: ArchAdam(mode='two'), one launch
         # (ops.alpha_two_step) for those three statements; with 'full' the keyword changes nothing
         self.fused_arch_update = bool(fused_arch_update) and arch_mode == 'two'
+        cost_kw = dict(cost=cost_table, cost_weight=cost_weight, cost_form=cost_form, cost_ref=cost_ref)
         if arch_mode == 'full':
-            self.alpha_optim = ArchAdam(net, alpha_lr, alpha_betas, weight_decay=alpha_weight_decay)
+            self.alpha_optim = ArchAdam(net, alpha_lr, alpha_betas, weight_decay=alpha_weight_decay, **cost_kw)
         elif self.fused_arch_update:
-            self.alpha_optim = ArchAdam(net, alpha_lr, alpha_betas, weight_decay=alpha_weight_decay, mode='two')
+            self.alpha_optim = ArchAdam(net, alpha_lr, alpha_betas, weight_decay=alpha_weight_decay, mode='two', **cost_kw)
         else:
             net._flat_alphas()          # (the parameters' storage moves into the flat blocks before Adam sees them)
             self.alpha_optim = torch.optim.Adam(list(net.alpha_prob_parameters()), alpha_lr, betas=tuple(alpha_betas),

@@ -614,6 +614,20 @@ class NetSearchBase(_Net):
             gene[kind].append([OPS_ADAPTER.Used_OPS[kind][int(torch.argmax(p.data))]])
         return gene
 
+    def expected_cost(self, block):
+        """E = sum over the nodes of softmax(alpha) . cost for a [nodes, width] cost block (mmnas_amd.cost): a device scalar,
+        nothing is read back."""
+        prob, _ = self._flat_alphas()
+        with torch.no_grad():
+            return (torch.softmax(prob, dim=1) * block.to(prob.device, prob.dtype)).sum()
+
+    def genotype_cost(self, block):
+        """The cost of the architecture genotype() names (every node's argmax candidate), as a float."""
+        prob, _ = self._flat_alphas()
+        with torch.no_grad():
+            pick = torch.argmax(prob, dim=1, keepdim=True)
+            return float(block.to(prob.device, prob.dtype).gather(1, pick).sum())
+
     def genotype_weights(self):
         w = {'w_enc': [], 'w_dec': []}
         with torch.no_grad():

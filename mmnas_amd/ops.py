@@ -1794,6 +1794,115 @@ def alpha_two_step(prob, gate_grad, m, v, prob_grad, pairs, lr, betas, eps, step
         _alpha_two_step_torch(prob, gate_grad, m, v, prob_grad, idx, float(lr), betas, float(eps), int(step), float(weight_decay))
 
 
+COST_FORMS = ('linear', 'log')        # cost_form of mmnas_alpha_*_step_cost: 0, 1
+
+
+def alpha_expected_cost(prob, cost, cost_weight, cost_ref, cost_form):
+    """The expected-cost term of a hardware-aware search over the [rows, width] alpha block (padding columns -inf in prob,
+    0 in cost): p = softmax(prob) per row, E_r = sum_j p_j cost[r, j], E = sum_r E_r and
+      'linear': R = cost_weight * (E - cost_ref) / cost_ref, k = cost_weight / cost_ref
+      'log':    R = cost_weight * log(E / cost_ref),          k = cost_weight / E      (E <= 0: both 0)
+    Returns (p, E_r, E, R, k); dR/dprob = k * p * (cost - E_r).  Tensors throughout: nothing is read back."""
+    p = torch.softmax(prob, dim=1)
+    er = (p * cost).sum(dim=1)
+    E = er.sum()
+    if cost_form == 'linear':
+        return p, er, E, cost_weight * (E - cost_ref) / cost_ref, torch.full_like(E, cost_weight / cost_ref)
+    pos = E > 0
+    safe = torch.where(pos, E, torch.ones_like(E))
+    zero = torch.zeros_like(E)
+    return p, er, E, torch.where(pos, cost_weight * torch.log(safe / cost_ref), zero), torch.where(pos, cost_weight / safe, zero)
+
+
+def _alpha_cost_step_torch(prob, gate_grad, m, v, prob_grad, cost, idx, lr, betas, eps, step, weight_decay, cost_weight, cost_ref,
+                           cost_form, stats):
+    """mmnas_alpha_full_step_cost (idx None) / mmnas_alpha_two_step_cost (idx [rows, 2]), statement for statement, in the
+    tensors' own dtype."""
+    b1, b2 = float(betas[0]), float(betas[1])
+    c1 = 1.0 - b1 ** step
+    c2s = math.sqrt(1.0 - b2 ** step)
+    p, er, E, R, k = alpha_expected_cost(prob, cost, cost_weight, cost_ref, cost_form)      # from the alphas before the update
+    if idx is None:
+        grad = p * (gate_grad - (gate_grad * p).sum(dim=1, keepdim=True))                   # 'full': mixed.py:194-198
+    else:
+        old = prob.gather(1, idx)
+        grad = alpha_two_pair_grad(prob, gate_grad, idx)
+    grad = grad + k * p * (cost - er.unsqueeze(1))
+    if prob_grad is not None:
+        prob_grad.copy_(grad)
+    if stats is not None:
+        stats[:-2].copy_(er)
+        stats[-2].copy_(E)
+        stats[-1].copy_(R)
+    valid = prob > float('-inf')                      # padding columns: logit, m and v stay as they are
+    if weight_decay:
+        grad = grad + weight_decay * torch.where(valid, prob, torch.zeros_like(prob))
+    mi = b1 * m + (1.0 - b1) * grad
+    vi = b2 * v + (1.0 - b2) * grad * grad
+    m.copy_(torch.where(valid, mi, m))
+    v.copy_(torch.where(valid, vi, v))
+    prob.copy_(torch.where(valid, prob - (lr / c1) * mi / (vi.sqrt() / c2s + eps), prob))
+    if idx is not None:
+        alpha_two_rescale(prob, old, idx)
+
+
+def alpha_cost_step(prob, gate_grad, m, v, prob_grad, cost, lr, betas, eps, step, weight_decay=0.0, cost_weight=0.0, cost_ref=1.0,
+                    cost_form='linear', pairs=None, stats=None):
+    """The architecture update with the expected-cost regulariser R of alpha_expected_cost() in the objective, one launch
+    (mmnas_alpha_full_step_cost; with `pairs`, one (active, inactive) column pair per node as in alpha_two_step,
+    mmnas_alpha_two_step_cost).  The cost gradient k p_j (cost_j - E_r), p the softmax over the whole row, reaches every live
+    column in both modes; in 'two' mode the task gradient stays the one over the sampled pair and the pair is rescaled after
+    Adam as in alpha_two_step.  prob_grad (or None) receives task part + cost part; `stats` (or None; rows + 2) E_r per row,
+    E, R -- all from the alphas before the update.  cost [rows, width]: 0 in the padding columns.
+    CUDA float32 tensors take the kernels; CPU tensors of any float dtype the same arithmetic in torch."""
+    rows, width = prob.shape
+    who = 'alpha_cost_step'
+    if cost_form not in COST_FORMS:
+        raise ValueError("%s: cost_form is 'linear' or 'log', got %r" % (who, cost_form))
+    cost_weight, cost_ref = float(cost_weight), float(cost_ref)
+    if not (math.isfinite(cost_ref) and cost_ref > 0):
+        raise ValueError('%s: cost_ref must be finite and positive, got %r' % (who, cost_ref))
+    if not (math.isfinite(cost_weight) and cost_weight >= 0):
+        raise ValueError('%s: cost_weight must be finite and not negative, got %r' % (who, cost_weight))
+    if int(step) < 1:
+        raise ValueError('%s: step counts from 1, got %r' % (who, step))
+    if width < (1 if pairs is None else 2):
+        raise ValueError('%s: width %d' % (who, width))
+    if pairs is not None:
+        pairs = [(int(p[0]), int(p[1])) for p in pairs]
+        if len(pairs) != rows:
+            raise ValueError('%s: %d pairs for %d rows' % (who, len(pairs), rows))
+        if rows > ALPHA_TWO_MAX_ROWS:
+            raise ValueError('%s: %d rows with pairs, at most %d' % (who, rows, ALPHA_TWO_MAX_ROWS))
+        for r, (i, j) in enumerate(pairs):
+            if not (0 <= i < width and 0 <= j < width) or i == j:
+                raise ValueError('%s: row %d: pair (%d, %d) must be two different columns of 0..%d' % (who, r, i, j, width - 1))
+    ts = [t for t in (prob, gate_grad, m, v, prob_grad, cost) if t is not None]
+    if cost is None or any(tuple(t.shape) != (rows, width) or t.device != prob.device for t in ts):
+        raise ValueError('%s: prob, gate_grad, m, v, prob_grad and cost share one [rows, width] shape and one device' % who)
+    if stats is not None and (tuple(stats.shape) != (rows + 2,) or stats.device != prob.device):
+        raise ValueError('%s: stats holds rows + 2 = %d values on the device of prob' % (who, rows + 2))
+    form = COST_FORMS.index(cost_form)
+    if prob.is_cuda and rows:
+        hyper = (float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), cost_weight, cost_ref, form, int(step),
+                 L.stream())
+        ptrs = [L.fptr(t) for t in (prob, gate_grad, m, v, prob_grad, cost, stats)]
+        if pairs is None:
+            L.check(L.lib().mmnas_alpha_full_step_cost(*ptrs, rows, width, *hyper))
+        else:
+            arr = (C.c_int * (2 * rows))(*[c for p in pairs for c in p])
+            L.check(L.lib().mmnas_alpha_two_step_cost(*ptrs, rows, width, arr, *hyper))
+        return
+    idx = None
+    if pairs is not None and rows:
+        idx = torch.tensor(pairs, dtype=torch.int64, device=prob.device)
+        if bool(torch.isinf(prob.gather(1, idx)).any()):      # (host tensors: the logits are at hand)
+            raise ValueError('%s: a pair names a padding column' % who)
+    with torch.no_grad():      # (also a device block without rows: nothing to launch over, E = 0)
+        _alpha_cost_step_torch(prob, gate_grad, m, v, prob_grad, cost, idx, float(lr), betas, float(eps), int(step),
+                               float(weight_decay), cost_weight, cost_ref, cost_form, stats)
+
+
 def row_is_zero(feature):
     """make_mask (hygr_vqa.py:121-122) for a float feature tensor [..., d]: True where the whole row is zero."""
     f = _f32c(feature)
