@@ -226,6 +226,9 @@ int mmnas_gemm_reload_tuning(void);
  *         ws: NULL -> the column reductions use float atomics; otherwise a scratch buffer of
  *         mmnas_layernorm_bwd_ws_floats(M, d) floats -> per-workgroup partial rows + a second
  *         pass (no atomics on 3*d hot addresses, bitwise reproducible).
+ *         A constant row (std == 0) gets dx = (dy*a - mean(dy*a)) / eps: the std term is dropped
+ *         there, as torch's autograd of the module masks std's backward to 0 -- finite, not 0/0.
+ *         Rows whose std^3 * d overflows float32 (std above ~1e12) keep the std term.
  * d % 4 == 0, d <= 2048.
  * ------------------------------------------------------------------------------------------ */
 int mmnas_layernorm_fwd(const float* x, const float* a, const float* b, float* y,
@@ -333,6 +336,14 @@ int mmnas_node_mix_fwd(const float* const* z, const float* const* ln_a, const fl
 int mmnas_node_mix_bwd(const float* const* z, const float* const* ln_a, const float* const* ln_b, int n, const float* gate,
                        const float* dout, float* d_active, int active, float* dgate, float* ws, int M, int d, float eps,
                        void* stream);
+/* The same backward with the sampled candidate's LayerNorm backward inside the launch (what the mixed chain runs for d <= 256;
+ * candidate `active` must be evaluated and carry LayerNorm parameters): instead of d_active it writes dz [M,d] = the gradient wrt
+ * z[active], dt (nullable) = dz behind the candidate's output dropout (drop_p, seed, site; index row*d+col) and ADDS the LayerNorm
+ * parameter gradients onto dln_a / dln_b [d] and the column sums of dt onto dcol [d] (each nullable; dcol needs dt).
+ * lnws: mmnas_layernorm_bwd_ws_floats(M, d) floats.  Constant rows and overflow as mmnas_layernorm_bwd. */
+int mmnas_node_mix_bwd_ln(const float* const* z, const float* const* ln_a, const float* const* ln_b, int n, const float* gate,
+                          const float* dout, int active, float* dgate, float* ws, float* dz, float* dt, float* dln_a, float* dln_b,
+                          float* dcol, float* lnws, float drop_p, uint64_t seed, uint32_t site, int M, int d, float eps, void* stream);
 int mmnas_mixed_sum_fwd(const float* const* outs_host, int n, const float* gate, float* out, size_t count,
                         void* stream);
 int mmnas_mixed_sum_bwd(const float* const* outs_host, int n, const float* gate, const float* dout,

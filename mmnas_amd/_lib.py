@@ -204,6 +204,7 @@ SYMBOLS = {
     'mmnas_embedding_bwd': (_i, [_fp, _fp, _fp, C.c_long, _i, C.c_long, _fp]),
     'mmnas_node_mix_fwd': (_i, [_fp, _fp, _fp, _i, _fp, _fp, _i, _i, _f, _fp]),
     'mmnas_node_mix_bwd': (_i, [_fp, _fp, _fp, _i, _fp, _fp, _fp, _i, _fp, _fp, _i, _i, _f, _fp]),
+    'mmnas_node_mix_bwd_ln': (_i, [_fp, _fp, _fp, _i, _fp, _fp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _f, _u64, _u32, _i, _i, _f, _fp]),
     'mmnas_embedding_bwd_det': (_i, [_fp, _fp, _fp, _fp, C.c_long, _i, C.c_long, _f, _fp]),
     'mmnas_embedding_bwd_det_ws_floats': (_sz, [C.c_long, _i]),
     'mmnas_rel_fused_supported': (_i, [_i, _i, _i]),

@@ -300,7 +300,7 @@ __global__ void __launch_bounds__(256) node_mix_bwd_kernel(NodeMixArgs p, const 
           const float sden = sd + eps;
           const float inv = 1.0f / sden;
           const float mg = sg / (float)d;
-          const float k2 = sgc / ((float)(d - 1) * sd * sden * sden);
+          const float k2 = ln_bwd_k2(sgc, (float)(d - 1), 1.0f / (float)(d - 1), sd, sden, inv);
 #pragma unroll
           for (int i = 0; i < NV; ++i) {
             const int c = (lane + 64 * i) * 4;
@@ -749,6 +749,26 @@ extern "C" int mmnas_node_mix_bwd(const float* const* z, const float* const* ln_
                                   const float* dout, float* d_active, int active, float* dgate, float* ws, int M, int d, float eps,
                                   void* stream) {
   return mmnas::node_mix_bwd_impl(z, ln_a, ln_b, n, gate, dout, d_active, active, dgate, ws, M, d, eps, (hipStream_t)stream, true, nullptr);
+}
+
+// mmnas_node_mix_bwd with the sampled candidate's LayerNorm backward inside the same launch, as the mixed chain runs it
+// (ops.hip: chain backward): dz / dt / the LayerNorm parameter gradients instead of d_active.
+extern "C" int mmnas_node_mix_bwd_ln(const float* const* z, const float* const* ln_a, const float* const* ln_b, int n, const float* gate,
+                                     const float* dout, int active, float* dgate, float* ws, float* dz, float* dt, float* dln_a,
+                                     float* dln_b, float* dcol, float* lnws, float drop_p, uint64_t seed, uint32_t site, int M, int d,
+                                     float eps, void* stream) {
+  MMNAS_REQUIRE(dz && lnws && ln_a && ln_b, MMNAS_E_ARG, "mmnas_node_mix_bwd_ln: null pointer");
+  MMNAS_REQUIRE(dcol == nullptr || dt != nullptr, MMNAS_E_ARG, "mmnas_node_mix_bwd_ln: dcol needs dt");
+  mmnas::NodeLnBwd lnb;
+  lnb.dz = dz; lnb.dt = dt; lnb.part = lnws;
+  lnb.drop = mmnas::make_drop(dt ? drop_p : 0.f, seed, site);
+  int nwg = 0;
+  const int rc = mmnas::node_mix_bwd_impl(z, ln_a, ln_b, n, gate, dout, nullptr, active, dgate, ws, M, d, eps, (hipStream_t)stream, true, &nwg, &lnb);
+  if (rc || nwg == 0) return rc;
+  mmnas::AuxReduce aux;
+  aux.part = lnws; aux.nrows = nwg; aux.d = d;
+  aux.out[0] = dln_a; aux.out[1] = dln_b; aux.out[2] = dcol;
+  return mmnas::launch_aux_reduce(aux, (hipStream_t)stream);
 }
 
 int mmnas::node_mix_bwd_impl(const float* const* z, const float* const* ln_a, const float* const* ln_b, int n, const float* gate,

@@ -52,7 +52,8 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(const float* __restrict__ x
 
 // ---------------------------------------------------------------- LayerNorm backward
 // dx = (g - mean(g))/s - c * sum(g*c) / ((n-1) * sd * s^2),  g = dy*a, c = x-mean, s = sd+eps
-// (pinned by oracle.layer_norm_backward against the reference's autograd).
+// (pinned by oracle.layer_norm_backward against the reference's autograd).  The second term's coefficient
+// is ln_bwd_k2 (common.h): 0 on a constant row, overflow-safe on huge ones; tests/test_ln_rows_gpu.py.
 template <int NV>
 __global__ void __launch_bounds__(256) ln_bwd_kernel(const float* __restrict__ x, const float* __restrict__ a,
                                                      const float* __restrict__ dy, float* __restrict__ dx,
@@ -118,7 +119,7 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(const float* __restrict__ x
     const float sden = sd + eps;
     const float inv = 1.0f / sden;
     const float mg = sg / (float)d;
-    const float k2 = sgc / ((float)(d - 1) * sd * sden * sden);
+    const float k2 = ln_bwd_k2(sgc, (float)(d - 1), 1.0f / (float)(d - 1), sd, sden, inv);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int c = (lane + 64 * i) * 4;

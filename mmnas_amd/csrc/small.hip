@@ -421,7 +421,7 @@ __global__ void __launch_bounds__(256, 1) sa_small_bwd_kernel(const SaSmallBwdK 
       const float sden = sd + p.eps;
       const float inv = 1.0f / sden;
       const float mg = sg / (float)D;
-      const float k2 = sgc / ((float)(D - 1) * sd * sden * sden);
+      const float k2 = ln_bwd_k2(sgc, (float)(D - 1), 1.0f / (float)(D - 1), sd, sden, inv);
 #pragma unroll
       for (int i = 0; i < NV; ++i) {
         const float4 gg = grow[i];

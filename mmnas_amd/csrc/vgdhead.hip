@@ -221,7 +221,11 @@ __global__ void __launch_bounds__(VH_BWD_THREADS) vgd_head_bwd_kernel(
     }
     sg = wave_sum(sg); sgc = wave_sum(sgc);
     const float mg = sg / (float)F;
-    const float k2 = sgc / ((float)(F - 1) * sd * sden * sden);
+    // sd is recovered from 1 / (sd + eps), so it is not exactly 0 on a constant row.  That needs no flag from the forward:
+    // there cv == 0 exactly, so sgc == 0 and the term is 0 whichever way ln_bwd_k2 decides.  A row whose recovered sd is not
+    // above 0 although its sd is (an estimate: sd within a few units in the last place of eps, ~1e-13) loses a term that is
+    // at most sd / (sd + eps), about 2e-7, of the first one.
+    const float k2 = ln_bwd_k2(sgc, (float)(F - 1), 1.0f / (float)(F - 1), sd, sden, inv);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int c = (lane + 64 * i) * 4;

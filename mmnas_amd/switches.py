@@ -84,6 +84,7 @@ DP_EARLY_SCATTER = _flag('MMNAS_DP_EARLY_SCATTER', False, 'is1', 'every_call', "
 LIB_PATH = _flag('MMNAS_LIB_PATH', None, 'string', 'doc', 'path of the shared library to load instead of mmnas_amd/lib/libmmnas_hip.so (tuning builds; read when _lib.py is imported)')
 _flag('MMNAS_REFERENCE_ROOT', None, 'string', 'doc', "a checkout of the reference whose mmnas/ package is merged behind this repository's (mmnas/__init__.py)")
 _flag('MMNAS_PROF_DUMP', None, 'string', 'doc', 'file the native profiler appends one row per bracketed launch to (csrc/util.hip)')
+_flag('MMNAS_LN_ROWS_STATS', None, 'string', 'doc', 'file tests/test_ln_rows_gpu.py writes the worst LayerNorm error per (kernel, row class, output) to (tests/ln_rows.py)')
 
 
 @contextlib.contextmanager

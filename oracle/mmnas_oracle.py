@@ -124,14 +124,18 @@ def layer_norm(x, a_2, b_2, eps=1e-6):
 
 
 def layer_norm_backward(x, a_2, dy, eps=1e-6):
-    """Closed-form backward of layer_norm; used to pin the HIP kernel's formula."""
+    """Closed-form backward of layer_norm; used to pin the HIP kernel's formula.
+    A constant row (sd == 0) has no std term: the reference's autograd masks std's backward to 0 there, which leaves
+    dx = (g - mean(g)) / eps; the unguarded quotient is 0 / 0."""
     n = x.shape[-1]
     mu = x.mean(-1, keepdim=True)
     c = x - mu
     sd = torch.sqrt((c * c).sum(-1, keepdim=True) / (n - 1))
     s = sd + eps
     g = dy * a_2
-    dx = (g - g.mean(-1, keepdim=True)) / s - c * (g * c).sum(-1, keepdim=True) / ((n - 1) * sd * s * s)
+    k2 = torch.where(sd > 0, (g * c).sum(-1, keepdim=True) / ((n - 1) * torch.where(sd > 0, sd, torch.ones_like(sd)) * s * s),
+                     torch.zeros_like(sd))
+    dx = (g - g.mean(-1, keepdim=True)) / s - c * k2
     red = tuple(range(x.dim() - 1))
     da = (dy * c / s).sum(red)
     db = dy.sum(red)
