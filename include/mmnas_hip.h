@@ -586,8 +586,9 @@ typedef struct mmnas_att_op {
   float* dWy; float* dby;                              /* accumulated (+=) */
   /* PACKED rows (ragged batches without their padding rows; see mmnas_mha_desc.q_off): q_off != NULL -- xq / y / dy / dxq
    * hold Mq = q_off[B] rows, sample b owning rows q_off[b] .. q_off[b+1]; Sq is the maximum length.  k_off / Mk likewise
-   * for xkv / dxkv (MMNAS_F_SELF: k_off = q_off; a guided operator keeps padded keys + mask: k_off = NULL).  With packed
-   * keys there is no mask.  MMNAS_F_REL then needs MMNAS_F_RELRAW + MMNAS_F_SELF and the relation tiles of
+   * for xkv / dxkv (MMNAS_F_SELF: k_off = q_off; a guided operator over padded keys + mask: k_off = NULL).  Either side may
+   * be packed alone: k_off without q_off is a guided operator from dense queries to the packed keys of a ragged language
+   * stream (mmnas_chain.x_off).  With packed keys there is no mask.  MMNAS_F_REL then needs MMNAS_F_RELRAW + MMNAS_F_SELF and the relation tiles of
    * mmnas_rel_fused_bwd_ragged (rel_tile_off [B+1] device, rel_ntiles host).  Sequences are prefixes: sample b's valid
    * rows are 0 .. n_b - 1 of its S. */
   const int* q_off; const int* k_off;
@@ -707,6 +708,18 @@ typedef struct mmnas_chain {
   const int* y_off;
   const int* y_tile_off;
   int Ny, y_ntiles;
+  /* RAGGED language stream: x_off != NULL -- x_in / x_out / dx_out / dx_in hold Nx = x_off[B] PACKED rows (sample b: rows
+   * x_off[b] .. x_off[b+1], its first n_b tokens; the caller packs, the head's language side takes packed rows).  Every
+   * encoder operator runs on Nx rows, self-attention over a sample's own rows without a mask (q_off = k_off = x_off); every
+   * guided operator reads packed keys (k_off = x_off, Mk = Nx, no mask) from dense or y_off queries.  x_mask is ignored.
+   * The padding tokens of the reference's language stream follow the valid ones, are masked as keys in every encoder
+   * self-attention and every guided attention and dropped by AttFlat's mask (hygr_vqa.py:113-122, modules.py:78-84,195-196):
+   * no logit and no parameter gradient depends on them -- the argument of y_off.  Needs 0 < Nx <= B * Sx, Sx <= 128 (with a
+   * guided operator also Sy <= 128: the packed attention cores), a single stream and no encoder operator with MMNAS_F_REL,
+   * else MMNAS_E_ARG.  (Appended: a zero-initialised descriptor of a caller built against the shorter struct must be
+   * rebuilt.) */
+  const int* x_off;
+  int Nx, reserved3;
 } mmnas_chain;
 int mmnas_chain_plan(const mmnas_chain* c, size_t* arena_bytes);   /* host only */
 int mmnas_chain_fwd(const mmnas_chain* c, void* stream);

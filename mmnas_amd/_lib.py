@@ -106,7 +106,8 @@ class Chain(C.Structure):
                 ('y_rel', _fp), ('arena', _fp), ('x_out', _fp), ('y_out', _fp), ('dx_out', _fp), ('dy_out', _fp),
                 ('dx_in', _fp), ('dy_in', _fp), ('use_side_stream', C.c_int), ('reserved', C.c_int),
                 ('marks', C.c_void_p), ('mixed', C.c_int), ('gate_width', C.c_int), ('gate', _fp), ('dgate', _fp),
-                ('y_off', _fp), ('y_tile_off', _fp), ('Ny', C.c_int), ('y_ntiles', C.c_int)]
+                ('y_off', _fp), ('y_tile_off', _fp), ('Ny', C.c_int), ('y_ntiles', C.c_int),
+                ('x_off', _fp), ('Nx', C.c_int), ('reserved3', C.c_int)]
 
 
 CHAIN_MAX_OPS = 128

@@ -100,12 +100,14 @@ static int att_check(const mmnas_att_op* op, const char* who) {
                 op->d, op->di);
   if (op->flags & MMNAS_F_SELF) MMNAS_REQUIRE(op->Sq == op->Sk, MMNAS_E_SHAPE, "%s: SELF needs Sq == Sk", who);
   if (op->q_off || op->k_off) {   // packed rows
-    MMNAS_REQUIRE(op->q_off && op->Mq > 0 && op->Mq <= op->B * op->Sq, MMNAS_E_ARG, "%s: packed rows: q_off / Mq=%d", who, op->Mq);
+    // (either side alone may be packed: packed keys under dense queries is a guided operator over a ragged language stream --
+    //  every attention core reads q_off and k_off independently)
+    MMNAS_REQUIRE(!op->q_off || (op->Mq > 0 && op->Mq <= op->B * op->Sq), MMNAS_E_ARG, "%s: packed rows: Mq=%d", who, op->Mq);
     MMNAS_REQUIRE(!op->k_off || (op->Mk > 0 && op->Mk <= op->B * op->Sk), MMNAS_E_ARG, "%s: packed rows: Mk=%d", who, op->Mk);
     if (op->flags & MMNAS_F_SELF) MMNAS_REQUIRE(op->k_off == op->q_off && op->Mk == op->Mq, MMNAS_E_ARG, "%s: packed SELF needs k_off == q_off", who);
     MMNAS_REQUIRE(!(op->k_off && (op->flags & MMNAS_F_MASK)), MMNAS_E_ARG, "%s: packed keys carry no mask", who);
     if (op->flags & MMNAS_F_REL)
-      MMNAS_REQUIRE((op->flags & MMNAS_F_RELRAW) && (op->flags & MMNAS_F_SELF) && op->rel_tile_off && op->rel_ntiles >= 0, MMNAS_E_ARG,
+      MMNAS_REQUIRE((op->flags & MMNAS_F_RELRAW) && (op->flags & MMNAS_F_SELF) && op->q_off && op->rel_tile_off && op->rel_ntiles >= 0, MMNAS_E_ARG,
                     "%s: a relation bias on packed rows needs the lazy handle (RELRAW), SELF and the relation tile offsets", who);
   }
   return MMNAS_OK;
@@ -668,6 +670,8 @@ static int chain_check(const mmnas_chain* c, const char* who) {
   MMNAS_REQUIRE(c->B > 0 && c->Sx > 0 && c->Sy > 0 && c->d > 0, MMNAS_E_SHAPE, "%s: B=%d Sx=%d Sy=%d d=%d", who, c->B, c->Sx, c->Sy, c->d);
   if (c->y_off) MMNAS_REQUIRE(c->Ny > 0 && c->Ny <= c->B * c->Sy && c->Sy <= 128 && !c->use_side_stream, MMNAS_E_ARG,
                               "%s: ragged decoder stream: Ny=%d of B*Sy=%d rows, Sy=%d <= 128, single stream", who, c->Ny, c->B * c->Sy, c->Sy);
+  if (c->x_off) MMNAS_REQUIRE(c->Nx > 0 && c->Nx <= c->B * c->Sx && c->Sx <= 128 && !c->use_side_stream, MMNAS_E_ARG,
+                              "%s: ragged language stream: Nx=%d of B*Sx=%d rows, Sx=%d <= 128, single stream", who, c->Nx, c->B * c->Sx, c->Sx);
   bool seen_y = false;
   for (int i = 0; i < c->n_ops; ++i) {
     const mmnas_chain_op& o = c->ops[i];
@@ -676,6 +680,13 @@ static int chain_check(const mmnas_chain* c, const char* who) {
     else MMNAS_REQUIRE(!seen_y, MMNAS_E_ARG, "%s: encoder operators must precede the decoder's (operator %d)", who, i);
     if (o.kind == MMNAS_CHAIN_ATT && !(o.att.flags & MMNAS_F_SELF))
       MMNAS_REQUIRE(o.on_y, MMNAS_E_ARG, "%s: operator %d: guided attention needs the decoder stream", who, i);
+    if (c->x_off && o.kind == MMNAS_CHAIN_ATT) {
+      // the token relations stay a padded [B,Sx,Sx,C] tensor nobody tiles for packed rows; the packed cores: heads of 64, <= 128 queries
+      MMNAS_REQUIRE(o.on_y || !(o.att.flags & MMNAS_F_REL), MMNAS_E_ARG, "%s: operator %d: ragged language stream: no encoder operator with a relation bias", who, i);
+      if (!o.on_y || !(o.att.flags & MMNAS_F_SELF))
+        MMNAS_REQUIRE(o.att.dh == 64 && (!o.on_y || c->Sy <= 128), MMNAS_E_ARG,
+                      "%s: operator %d: ragged language stream: packed keys need heads of 64 (dh=%d) and Sy=%d <= 128", who, i, o.att.dh, c->Sy);
+    }
   }
   if (c->mixed) {
     MMNAS_REQUIRE(c->gate && c->gate_width >= 1 && c->gate_width <= MMNAS_MIXED_MAX, MMNAS_E_ARG, "%s: mixed chain without a gate block (width %d)", who, c->gate_width);
@@ -702,6 +713,8 @@ static int chain_check(const mmnas_chain* c, const char* who) {
 
 // rows of the decoder stream: B * Sy, or the packed row count of a ragged batch
 static inline size_t chain_rows_y(const mmnas_chain* c) { return c->y_off ? (size_t)c->Ny : (size_t)c->B * c->Sy; }
+// rows of the language stream: B * Sx, or the packed row count of a ragged language stream (x_off)
+static inline size_t chain_rows_x(const mmnas_chain* c) { return c->x_off ? (size_t)c->Nx : (size_t)c->B * c->Sx; }
 
 // operator i with its stream-dependent fields filled in (shapes, masks, relation tensors): all that chain_layout, which runs
 // before an arena exists, needs; the buffers come with chain_bind
@@ -719,12 +732,16 @@ static void chain_op_shapes(const mmnas_chain* c, int i, mmnas_att_op& a, mmnas_
       a.q_off = c->y_off; a.Mq = c->Ny;
       if (self) { a.k_off = c->y_off; a.Mk = c->Ny; mask = nullptr; a.rel_tile_off = c->y_tile_off; a.rel_ntiles = c->y_ntiles; }
     }
+    if (c->x_off && (!o.on_y || !self)) {   // ragged language stream: the keys of an encoder or guided operator are its packed rows
+      a.k_off = c->x_off; a.Mk = c->Nx; mask = nullptr;
+      if (!o.on_y) { a.q_off = c->x_off; a.Mq = c->Nx; }
+    }
     a.mask = mask;
     if (mask) a.flags |= MMNAS_F_MASK; else a.flags &= ~MMNAS_F_MASK;
     if (a.flags & MMNAS_F_REL) a.rel = o.on_y ? c->y_rel : c->x_rel;
   } else {
     m = o.mlp;
-    m.M = (o.on_y && c->y_off) ? c->Ny : c->B * S;
+    m.M = o.on_y ? (int)chain_rows_y(c) : (int)chain_rows_x(c);
   }
 }
 
@@ -741,7 +758,7 @@ static int chain_layout(const mmnas_chain* c, ChainLayout& L) {
     if (c->ops[i].on_y) { if (L.first_y < 0) L.first_y = i; L.last_y = i; }
     else { if (L.first_x < 0) L.first_x = i; L.last_x = i; }
   }
-  const size_t nx = (size_t)c->B * c->Sx * c->d * sizeof(float), ny = chain_rows_y(c) * c->d * sizeof(float);
+  const size_t nx = chain_rows_x(c) * c->d * sizeof(float), ny = chain_rows_y(c) * c->d * sizeof(float);
   for (int i = 0; i < c->n_ops; ++i) {
     const mmnas_chain_op& o = c->ops[i];
     mmnas_att_op a; mmnas_mlp_op m;
@@ -1173,7 +1190,7 @@ static int chain_guided_kv_bwd(const mmnas_chain* c, const ChainLayout& L, const
     const int rc = mmnas_gemm_pair(&g, &w, st);
     if (rc) return rc;
   }
-  return add_many(srcs, ns, out, (size_t)c->B * c->Sx * c->d, st);
+  return add_many(srcs, ns, out, chain_rows_x(c) * c->d, st);
 }
 
 }  // namespace mmnas
@@ -1219,7 +1236,7 @@ static int chain_rel_prologue(const mmnas_chain* c, const ChainLayout& L, const 
 static int chain_rel_join(SideCtx* rsc, hipStream_t st) { return ev_fork(rsc->side, st, rsc->ovl[1]); }   // the image stream's bias exists from here on
 // Forward, chain exit: a stream without operators hands its input on
 static int chain_fwd_passthrough(const mmnas_chain* c, const ChainLayout& L, hipStream_t st) {
-  const size_t nx = (size_t)c->B * c->Sx * c->d * sizeof(float), ny = chain_rows_y(c) * c->d * sizeof(float);
+  const size_t nx = chain_rows_x(c) * c->d * sizeof(float), ny = chain_rows_y(c) * c->d * sizeof(float);
   if (L.last_x < 0 && hipMemcpyAsync(c->x_out, c->x_in, nx, hipMemcpyDeviceToDevice, st) != hipSuccess) return MMNAS_E_LAUNCH;
   if (L.last_y < 0 && hipMemcpyAsync(c->y_out, c->y_in, ny, hipMemcpyDeviceToDevice, st) != hipSuccess) return MMNAS_E_LAUNCH;
   return MMNAS_OK;
@@ -1253,7 +1270,7 @@ static int chain_live_table(const mmnas_chain* c, const ChainLayout& L, hipStrea
 static int chain_bwd_begin(ChainBwd& S, const mmnas_chain* c, const ChainLayout& L, hipStream_t st, SideQueue* sq, bool hoist) {
   S.c = c; S.L = &L; S.st = st; S.sq = sq;
   S.dpre = chain_buf(c, L.dpre); S.encdy = chain_buf(c, L.encdy);
-  S.ex = (size_t)c->B * c->Sx * c->d;
+  S.ex = chain_rows_x(c) * c->d;
   // before any operator's backward launch, on the caller's stream: a side stream's queued products run behind an event that
   // this stream records later
   if (int r = chain_live_table(c, L, st, &S.ktab)) return r;
@@ -1425,7 +1442,7 @@ static int chain_fwd_mixed(const mmnas_chain* c, hipStream_t st, const ChainLayo
       chain_cand_view(b, &zs[k], &as[k], &bs[k]);
       if (k + 1 > width) width = k + 1;
     }
-    const int M = c->ops[i0].on_y ? (int)chain_rows_y(c) : c->B * c->Sx;
+    const int M = c->ops[i0].on_y ? (int)chain_rows_y(c) : (int)chain_rows_x(c);
     if ((rc = mmnas_node_mix_fwd(zs, as, bs, width, c->gate + (size_t)c->ops[i0].node * c->gate_width, chain_out(c, L, i0), M, c->d, eps, st))) return rc;
     i0 = i1;
   }
@@ -1462,7 +1479,7 @@ static int chain_bwd_mixed(const mmnas_chain* c, hipStream_t st, const ChainLayo
       if (b.flags() & MMNAS_F_NORM) eps = b.eps();
     }
     float* dact = chain_node_dact(c, L, i0);
-    const int M = c->ops[i0].on_y ? (int)chain_rows_y(c) : c->B * c->Sx;
+    const int M = c->ops[i0].on_y ? (int)chain_rows_y(c) : (int)chain_rows_x(c);
     const size_t grow = (size_t)c->ops[i0].node * c->gate_width;
     // The sampled candidate: its descriptor first -- its LayerNorm backward rides in the node's mix kernel (round 6) when the
     // epilogue's view carries the candidate's LayerNorm parameters, i.e. its own forward did not normalise, and the candidate

@@ -129,7 +129,11 @@ class DevicePrefetcher:
     0 .. n_b - 1 are its regions (non-zero rows) and rows n_b .. S - 1 are all-zero -- the same rows the networks' masks
     (make_mask: all-zero feature rows) call padding.  The counts are checked against the HOST copy of the features before
     the upload, because the ragged stream trusts them: `validate` = 'boundary' (default: row n_b - 1 non-zero, row n_b
-    all-zero -- two rows per sample), 'full' (every row: one pass over the batch on the host) or None."""
+    all-zero -- two rows per sample), 'full' (every row: one pass over the batch on the host) or None.
+    lengths may also be a LIST of such pairs -- regions and tokens: a pair whose features element is a 2-D integer tensor
+    (token indices [B, T], 0 = padding behind the words: load_data_vqa.py proc_ques) attaches the word counts that
+    ops.language_plan reads when the ragged language stream is on (ops.set_unpad_x); with `validate` set every token of the
+    host copy is checked (non-zero below the count, zero from it on: B * T integers)."""
 
     def __init__(self, loader, device, lengths=None, validate='boundary'):
         self.loader = loader
@@ -157,13 +161,32 @@ class DevicePrefetcher:
         else:
             with torch.cuda.stream(self.stream):
                 out = self._map(batch, lambda t: (t if t.is_pinned() else t.pin_memory()).to(self.device, non_blocking=True))
-        if self.lengths is not None:
-            fk, lk = self.lengths
+        for fk, lk in self._length_pairs():
             lens = [int(v) for v in self._to_tensor(batch[lk]).reshape(-1).tolist()]   # host values: no sync
+            feat = self._to_tensor(batch[fk])
             if self.validate:
-                self._check_lengths(self._to_tensor(batch[fk]), lens)
+                (self._check_tokens if feat.dim() == 2 and not feat.is_floating_point() else self._check_lengths)(feat, lens)
             out[fk]._mmnas_lengths = lens
         return out
+
+    def _length_pairs(self):
+        if self.lengths is None:
+            return []
+        if len(self.lengths) == 2 and not isinstance(self.lengths[0], (tuple, list)):
+            return [tuple(self.lengths)]
+        return [tuple(p) for p in self.lengths]
+
+    def _check_tokens(self, ix, lens):
+        """The word counts against the zero-token padding the networks' language mask is derived from."""
+        if ix.is_cuda or len(lens) != ix.shape[0]:
+            raise ValueError('DevicePrefetcher(lengths=...): %d counts for token indices of shape %s' % (len(lens), tuple(ix.shape)))
+        t = ix.detach().numpy()
+        n = np.asarray(lens, dtype=np.int64)
+        want = np.arange(t.shape[1])[None, :] < n[:, None]
+        bad = np.nonzero(((t != 0) != want).any(-1) | (n < 0) | (n > t.shape[1]))[0].tolist()
+        if bad:
+            raise ValueError('DevicePrefetcher: word counts disagree with the zero-token padding of the token indices for samples %s '
+                             '(count n_b: tokens < n_b non-zero, tokens >= n_b zero)' % bad[:8])
 
     def _check_lengths(self, feat, lens):
         """The region counts against the all-zero-row mask the networks derive from the same features (see CONTRACT)."""

@@ -107,7 +107,13 @@ def triplet_batch(pos, neg):
     def cat(i, a, b, c):
         if a[i] is None:
             return None
-        return torch.cat((a[i], b[i], c[i]), 0)
+        out = torch.cat((a[i], b[i], c[i]), 0)
+        # the parts' lengths (data.DevicePrefetcher(lengths=...)) travel with the batch: without them the ragged streams
+        # (ops.set_unpad / set_unpad_x) pay a device-to-host copy for every fresh 3B batch
+        lens = [getattr(t, '_mmnas_lengths', None) for t in (a[i], b[i], c[i])]
+        if all(l is not None for l in lens):
+            out._mmnas_lengths = [int(v) for l in lens for v in l]
+        return out
     return (cat(0, pos, pos, neg), cat(1, pos, pos, neg), cat(2, pos, pos, neg), cat(3, pos, neg, pos), cat(4, pos, neg, pos))
 
 

@@ -75,11 +75,14 @@ class _Backbone(nn.Module):
         self.cells_enc = nn.ModuleList([self.CELL(__C, type='enc') for _ in range(__C.LAYERS)])
         self.cells_dec = nn.ModuleList([self.CELL(__C, type='dec') for _ in range(__C.LAYERS)])
 
-    def _chain(self, x, y, x_mask, y_mask, x_rel_embed, y_rel_embed, packed=False):
+    def _chain(self, x, y, x_mask, y_mask, x_rel_embed, y_rel_embed, packed=False, x_ragged=None):
         """The whole backbone as ONE native call per direction (ops.BackboneFn) -- possible when every node holds a
         single attention- or MLP-family operator, relation operators can take the lazy handle, and every parameter's
         gradient lives in a flat buffer the kernels may add into (a reducer / FlatAdam is attached).  Returns None
-        when any of that does not hold: the per-operator path below serves every other case."""
+        when any of that does not hold: the per-operator path below serves every other case.
+        x_ragged (ops.Ragged; ops.set_unpad_x): `x` holds the PACKED rows of a ragged language stream and comes back packed.
+        None as well when an encoder operator carries a relation bias (the token relations stay a padded tensor: the caller
+        keeps the trimmed dense stream) or an operator's heads are not the packed attention cores' 64."""
         from .modules import FeedForward, FeedForward_deep, GuidedAtt, RelSelfAtt, SelfAtt
         if not (ops.chain_enabled() and x.is_cuda and x.dtype == torch.float32 and y.dtype == torch.float32):
             return None
@@ -105,6 +108,8 @@ class _Backbone(nn.Module):
             t = type(op)
             if t is SelfAtt or t is GuidedAtt or t is RelSelfAtt:
                 if t is GuidedAtt and not on_y:
+                    return None
+                if x_ragged is not None and (t is RelSelfAtt if not on_y else (t is GuidedAtt and y_mask is not None and y_mask.shape[-1] > 128)):
                     return None
                 rh = None
                 if t is RelSelfAtt:
@@ -240,6 +245,8 @@ class _Backbone(nn.Module):
                 op_params[g0] = list(op_params[g0]) + extra
         if not records or len(records) > 128:
             return None
+        if x_ragged is not None and any(r.kind == 0 and r.att.dh != 64 and not (r.on_y and r.att.flags & ops.L.F_SELF) for r in records):
+            return None
         xr = x_rel_embed.raw if isinstance(x_rel_embed, RelHandle) else None
         yr = y_rel_embed.raw if isinstance(y_rel_embed, RelHandle) else None
         # ragged decoder stream (ops.Ragged; MMNAS_UNPAD / ops.set_unpad): the net's forward attached the description of the
@@ -250,13 +257,21 @@ class _Backbone(nn.Module):
             ragged = None
         if packed and ragged is None:
             return None           # (packed image rows only make sense on the ragged stream: the caller falls back to padded rows)
+        if x_ragged is not None:
+            return ops.backbone_chain(x, y, x_mask, y_mask, xr, yr, records, params, op_params, mixed, ragged, packed, gviews, ptensors, x_ragged)
         return ops.backbone_chain(x, y, x_mask, y_mask, xr, yr, records, params, op_params, mixed, ragged, packed, gviews, ptensors)
 
-    def chain_packed(self, x, y_packed, x_mask, y_mask, x_rel_embed, y_rel_embed):
+    def chain_packed(self, x, y_packed, x_mask, y_mask, x_rel_embed, y_rel_embed, x_ragged=None):
         """The ragged decoder stream end to end: `y_packed` [sum n_b, d] are the projected VALID region rows (the stem ran
         on them only), the decoder output comes back packed (for the head's AttFlat over packed rows).  None when the chain
-        or the ragged stream cannot take this call -- the caller then projects the padded rows and calls forward()."""
-        return self._chain(x, y_packed, x_mask, y_mask, x_rel_embed, y_rel_embed, packed=True)
+        or the ragged stream cannot take this call -- the caller then projects the padded rows and calls forward().
+        x_ragged: `x` is the packed language stream as well (see _chain)."""
+        return self._chain(x, y_packed, x_mask, y_mask, x_rel_embed, y_rel_embed, packed=True, x_ragged=x_ragged)
+
+    def chain_packed_x(self, x_packed, y, x_mask, y_mask, x_rel_embed, y_rel_embed, x_ragged):
+        """The ragged LANGUAGE stream beside a padded image stream: `x_packed` [sum n_b, d] are the valid rows of the LSTM
+        output, the language state comes back packed (for the head's AttFlat over packed rows); None as chain_packed."""
+        return self._chain(x_packed, y, x_mask, y_mask, x_rel_embed, y_rel_embed, x_ragged=x_ragged)
 
     def forward(self, x, y, x_mask, y_mask, x_rel_embed, y_rel_embed):
         out = self._chain(x, y, x_mask, y_mask, x_rel_embed, y_rel_embed)
@@ -339,7 +354,17 @@ class _Net(nn.Module):
             # ragged decoder stream: only where the head drops the padding rows (AttFlat's mask; the grounding head scores
             # EVERY region row, padding included -- full_vgd.py:105-114 -- so it keeps the padded computation)
             y_mask._mmnas_ragged = ops.ragged_info_for(frcn_feat, y_mask)
+        # Ragged language stream (ops.set_unpad_x; off: lp is None and every line below is the padded path's).  The embedding
+        # runs on the UNTRIMMED indices (a data-parallel row exchange keeps gathering index lists of one size on every rank; the
+        # pad token's gradient rows are zero either way), everything behind it on the longest sample's T' tokens.
+        lp = ops.language_plan(ques_ix, x_mask) if ops.unpad_x_enabled() else None
         emb = ops.embedding(ques_ix, self.embedding)
+        if lp is not None and lp.T < ques_ix.shape[1]:
+            T0 = ques_ix.shape[1]
+            emb = emb[:, :lp.T]
+            x_mask = x_mask[..., :lp.T].contiguous()
+            if torch.is_tensor(x_rel_embed) and x_rel_embed.dim() == 4 and x_rel_embed.shape[1] == T0 and x_rel_embed.shape[2] == T0:
+                x_rel_embed = x_rel_embed[:, :lp.T, :lp.T].contiguous()
         # (one persistent launch per pass: ops.LstmFn; nn.LSTM = MIOpen only for shapes outside its range)
         x_in = ops.lstm(emb, self.lstm) if (ops.lstm_enabled() and ops.lstm_supported(emb, self.lstm)) else self.lstm(emb)[0]
         if C.BBOX_FEATURE:
@@ -363,16 +388,36 @@ class _Net(nn.Module):
         native_head = self.TASK != 'vgd' and ops.chain_enabled() and frcn_feat.is_cuda
         # (head_record() draws the head's dropout seeds: it stays BEHIND the backbone call, where the per-operator path draws
         #  them too -- the seed order is what lets dropout be replayed across the paths)
-        if rg is not None and native_head and ops._sinked((self.attflat_x.mlp.fc.linear.weight,)):
+        # the language stream packed under the same conditions (its LSTM output packed here, unpacked with zeros backward)
+        xrg = lp.ragged if lp is not None else None
+        sinks = native_head and ops._sinked((self.attflat_x.mlp.fc.linear.weight,))
+        if rg is not None and sinks:
             y_pk = ops.linear(ops.pack_rows_fn(frcn_feat, rg), self.imgfeat_linear.weight, self.imgfeat_linear.bias)
-            packed = self.backnone.chain_packed(x_in, y_pk, x_mask, y_mask, x_rel_embed, y_rel_embed)
+            if xrg is not None:
+                packed = self.backnone.chain_packed(ops.pack_rows_fn(x_in, xrg), y_pk, x_mask, y_mask, x_rel_embed, y_rel_embed, xrg)
+            if packed is None:
+                xrg = None
+                packed = self.backnone.chain_packed(x_in, y_pk, x_mask, y_mask, x_rel_embed, y_rel_embed)
+        elif xrg is not None and sinks:
+            y_in = ops.linear(frcn_feat, self.imgfeat_linear.weight, self.imgfeat_linear.bias)
+            packed = self.backnone.chain_packed_x(ops.pack_rows_fn(x_in, xrg), y_in, x_mask, y_mask, x_rel_embed, y_rel_embed, xrg)
+            if packed is None:       # (the chain cannot take the packed stream: trimmed and dense, below)
+                xrg = None
+        else:
+            xrg = None
         if packed is not None:
             x_out, y_out = packed
             hd, hp = ops.head_record(self.attflat_x, self.attflat_y, self.proj_norm, self.proj, self.training)
             if hd is not None:
-                out = ops.HeadFn.apply(x_out, y_out, x_mask, y_mask, hd, hp, rg)
+                if xrg is not None:
+                    out = ops.HeadFn.apply(x_out, y_out, x_mask, y_mask, hd, hp, rg, xrg)
+                else:
+                    out = ops.HeadFn.apply(x_out, y_out, x_mask, y_mask, hd, hp, rg)
                 return torch.sigmoid(out.squeeze(-1)) if self.TASK == 'itm' else out
-            y_out = ops.unpack_rows_fn(y_out, rg, frcn_feat.shape[0], frcn_feat.shape[1])   # (no native head after all)
+            if rg is not None:
+                y_out = ops.unpack_rows_fn(y_out, rg, frcn_feat.shape[0], frcn_feat.shape[1])   # (no native head after all)
+            if xrg is not None:
+                x_out = ops.unpack_rows_fn(x_out, xrg, x_mask.shape[0], x_mask.shape[-1])
         else:
             y_in = ops.linear(frcn_feat, self.imgfeat_linear.weight, self.imgfeat_linear.bias)
             x_out, y_out = self.backnone(x_in, y_in, x_mask, y_mask, x_rel_embed, y_rel_embed)

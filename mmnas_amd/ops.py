@@ -1370,6 +1370,90 @@ def _make_ragged(lens, B, S, device):
     return Ragged(lens, device)
 
 
+# ------------------------------------------------------------------------------------------
+# Ragged LANGUAGE stream (set_unpad_x; a Python-side switch without an environment variable, off by default).  The loaders pad
+# every question / caption with zero tokens behind its words -- ITM captions to the longest caption of the dataset
+# (load_data_itm.py:94-97).  The LSTM is causal and the padding follows the words; padded tokens are masked as keys in every
+# encoder self-attention and every guided attention and dropped by attflat_x's mask (modules.py:78-84,195-196): no logit and
+# no parameter gradient depends on them.  Two steps: TRIM the stream to the longest sample of the batch (plain slicing, every
+# task and path), and above 16 tokens PACK it (mmnas_chain.x_off: encoder on the valid rows only, guided operators over packed
+# keys, the head's language side over packed rows).  Independent of set_unpad.
+# ------------------------------------------------------------------------------------------
+_unpad_x = [False]
+
+
+def unpad_x_enabled():
+    return _unpad_x[0]
+
+
+def set_unpad_x(on):
+    """Switch the ragged language stream on / off (returns the previous setting)."""
+    prev = _unpad_x[0]
+    _unpad_x[0] = bool(on)
+    return prev
+
+
+def language_decision(lengths, T):
+    """The plan as a pure function of the token counts and the padded length T: None (no valid plan: an empty sample, a count
+    above T, no sample) or (T', pack) with T' = max(lengths).  pack: 16 < T' <= 128 and padding left after trimming -- at
+    T' <= 16 the one-launch short-sequence operators (small.hip) want dense rows and a 16-row tile gains nothing from packing;
+    above 128 the packed attention cores do not apply."""
+    if lengths is None or len(lengths) == 0 or min(lengths) < 1 or max(lengths) > T:
+        return None
+    Tp = max(lengths)
+    return Tp, bool(16 < Tp <= 128 and sum(lengths) < len(lengths) * Tp)
+
+
+class LanguagePlan:
+    """T: the trimmed length; ragged: the ops.Ragged of the packed stream (rows of the TRIMMED [B, T, d] layout) or None = the
+    trimmed stream stays dense; lengths: the token counts."""
+
+    def __init__(self, lengths, T, ragged):
+        self.lengths, self.T, self.ragged = tuple(lengths), T, ragged
+
+
+_language_cache = {}
+
+
+def language_plan(ques_ix, x_mask=None):
+    """Plan of the batch whose token indices are `ques_ix` [B, T] (0 = padding) and whose padding mask is `x_mask` (True =
+    padding; None: ques_ix == 0), or None = today's path: the switch is off, the tensor is on the CPU, the side stream is on
+    (mmnas_chain_bwd refuses packed rows there), a sample has no token, or the tokens of a sample are not a prefix.  The counts
+    come from `ques_ix._mmnas_lengths` when the data pipeline attached them (no synchronisation), else from the mask with ONE
+    device-to-host copy per distinct tensor (cached on the tensor object and its version counter, as ragged_info_for)."""
+    if not unpad_x_enabled() or not ques_ix.is_cuda or ques_ix.dim() != 2:
+        return None
+    if side_stream_enabled():
+        return None
+    B, T = ques_ix.shape
+    lens = getattr(ques_ix, '_mmnas_lengths', None)
+    if lens is not None:
+        lens = [int(v) for v in lens]
+        return _make_language_plan(lens if len(lens) == B else None, T, ques_ix.device)
+    key = id(ques_ix)
+    hit = _language_cache.get(key)
+    if hit is not None and hit[0]() is ques_ix and hit[1] == ques_ix._version:
+        return hit[2]
+    m = x_mask.reshape(B, T) if x_mask is not None else (ques_ix == 0)
+    n = (~m).sum(1)
+    ok = (m == (torch.arange(T, device=m.device)[None, :] >= n[:, None])).all()
+    host = torch.cat([n, ok.long().view(1)]).cpu()
+    plan = _make_language_plan(host[:B].tolist() if int(host[B]) else None, T, ques_ix.device)
+    import weakref
+    if len(_language_cache) > 64:
+        _language_cache.clear()
+    _language_cache[key] = (weakref.ref(ques_ix), ques_ix._version, plan)
+    return plan
+
+
+def _make_language_plan(lens, T, device):
+    got = language_decision(lens, T)
+    if got is None:
+        return None
+    Tp, pack = got
+    return LanguagePlan(lens, Tp, Ragged(lens, device) if pack else None)
+
+
 def pack_rows(x, rg):
     """[B, S, d] -> packed [rg.N, d]."""
     B, S, d = x.shape
@@ -1439,10 +1523,19 @@ class BackboneFn(torch.autograd.Function):
         aligned with them, the views of a per-call zero-filled buffer the kernels accumulate their gradients into (the
         descriptors in `records` point there); backward returns the views.
         packed_io (with ragged): `y` arrives PACKED [ragged.N, d] (the stem projected the valid region rows only) and the
-        decoder output is returned packed too (the head's AttFlat takes packed rows): no pack / unpack launches at all."""
+        decoder output is returned packed too (the head's AttFlat takes packed rows): no pack / unpack launches at all.
+        x_ragged (APPENDED behind ptensors: a trailing ops.Ragged; see backbone_chain): the ragged language stream -- `x`
+        arrives PACKED [x_ragged.N, d] (the stem packed the LSTM output), x_mask [B,1,1,Sx] still names B and the longest
+        sample Sx, and x_out is returned packed (the head's language side takes packed rows)."""
         lib = L.lib()
+        x_ragged = None
+        if ptensors and isinstance(ptensors[-1], Ragged):
+            x_ragged, ptensors = ptensors[-1], ptensors[:-1]
         x, y = _f32c(x), _f32c(y)
-        B, Sx, d = x.shape
+        if x_ragged is not None:
+            B, Sx, d = len(x_ragged.lengths), int(x_mask.shape[-1]), x.shape[-1]
+        else:
+            B, Sx, d = x.shape
         packed_io = bool(packed_io and ragged is not None)
         Sy = int(y_mask.shape[-1]) if packed_io else y.shape[1]
         if ragged is not None and not packed_io:     # the decoder stream on its valid rows only (see Ragged)
@@ -1461,6 +1554,8 @@ class BackboneFn(torch.autograd.Function):
             ch.mixed, ch.gate, ch.dgate, ch.gate_width = 1, mixed[0], mixed[1], mixed[2]
         if ragged is not None:
             ch.y_off, ch.y_tile_off, ch.Ny, ch.y_ntiles = L.ptr(ragged.off), L.ptr(ragged.tile_off), ragged.N, ragged.ntiles
+        if x_ragged is not None:
+            ch.x_off, ch.Nx = L.ptr(x_ragged.off), x_ragged.N
         sz = C.c_size_t()
         L.check(lib.mmnas_chain_plan(C.byref(ch), C.byref(sz)))   # (host arithmetic only: a few microseconds)
         arena = _bytes(sz.value, x.device)
@@ -1470,6 +1565,7 @@ class BackboneFn(torch.autograd.Function):
         ctx.keep = (ch, arr, arena, x, y, xm, ym, xr, yr, x_out, y_out, params)
         ctx.op_params = op_params
         ctx.ragged = (ragged, B, Sy, packed_io)
+        ctx.x_ragged = x_ragged     # (keeps the offsets alive until backward has been enqueued)
         ctx.gviews = gviews
         ctx.n_extra = len(ptensors)
         if gviews is not None:
@@ -1528,12 +1624,15 @@ class BackboneFn(torch.autograd.Function):
         head = (dx_in, dy_in, None, None, None, None, None, None, None, None, None, None, None)
         if ctx.gviews is not None:
             gv, ctx.gviews = ctx.gviews, None
-            return head + tuple(gv)
-        return head + (None,) * ctx.n_extra
+            return head + tuple(gv) + (None,)
+        return head + (None,) * (ctx.n_extra + 1)     # (+ the appended x_ragged, when there is one: a trailing None is ignored)
 
 
 def backbone_chain(x, y, x_mask, y_mask, x_rel, y_rel, records, params, op_params=None, mixed=None, ragged=None, packed_io=False,
-                   gviews=None, ptensors=()):
+                   gviews=None, ptensors=(), x_ragged=None):
+    if x_ragged is not None:      # the ragged language stream's description rides BEHIND the parameter tensors
+        return BackboneFn.apply(x, y, x_mask, y_mask, x_rel, y_rel, records, params, op_params, mixed, ragged, packed_io, gviews, *ptensors,
+                                x_ragged)
     return BackboneFn.apply(x, y, x_mask, y_mask, x_rel, y_rel, records, params, op_params, mixed, ragged, packed_io, gviews, *ptensors)
 
 
@@ -1542,12 +1641,18 @@ class HeadFn(torch.autograd.Function):
     per direction.  As for BackboneFn the parameters' gradients go straight into the flat gradient buffer."""
 
     @staticmethod
-    def forward(ctx, x, y, x_mask, y_mask, hd, params, ragged=None):
+    def forward(ctx, x, y, x_mask, y_mask, hd, params, ragged=None, x_ragged=None):
         """ragged (ops.Ragged): `y` holds the PACKED image rows [ragged.N, d] of a ragged decoder stream; AttFlat's masked
-        softmax runs over each sample's own rows (the mask hides exactly the padding rows: modules.py:78-81)."""
+        softmax runs over each sample's own rows (the mask hides exactly the padding rows: modules.py:78-81).
+        x_ragged: likewise `x` holds the PACKED language rows [x_ragged.N, d] of a ragged language stream."""
         lib = L.lib()
         x, y = _f32c(x), _f32c(y)
-        B, Sx, d = x.shape
+        if x_ragged is not None:
+            B, Sx, d = len(x_ragged.lengths), int(x_mask.shape[-1]), x.shape[-1]
+            hd.sx.off, hd.sx.M = L.ptr(x_ragged.off), x_ragged.N
+        else:
+            B, Sx, d = x.shape
+            hd.sx.off, hd.sx.M = None, 0
         if ragged is not None:
             Sy = int(y_mask.shape[-1])
             hd.sy.off, hd.sy.M = L.ptr(ragged.off), ragged.N
@@ -1562,16 +1667,16 @@ class HeadFn(torch.autograd.Function):
         nbytes = _plan_cache.get(key)
         if nbytes is None:
             sz = C.c_size_t()
-            off, M = hd.sy.off, hd.sy.M
-            hd.sy.off, hd.sy.M = None, 0
+            off, M, xoff, xM = hd.sy.off, hd.sy.M, hd.sx.off, hd.sx.M
+            hd.sy.off, hd.sy.M, hd.sx.off, hd.sx.M = None, 0, None, 0
             L.check(lib.mmnas_head_plan(C.byref(hd), C.byref(sz)))
-            hd.sy.off, hd.sy.M = off, M
+            hd.sy.off, hd.sy.M, hd.sx.off, hd.sx.M = off, M, xoff, xM
             nbytes = _plan_cache[key] = sz.value
         arena = _bytes(nbytes, x.device)
         logits = torch.empty(B, hd.ANS, dtype=torch.float32, device=x.device)
         hd.arena, hd.logits = L.ptr(arena), L.fptr(logits)
         L.check(lib.mmnas_head_fwd(C.byref(hd), L.stream()))
-        ctx.keep = (hd, arena, x, y, xm, ym, params, ragged)
+        ctx.keep = (hd, arena, x, y, xm, ym, params, ragged, x_ragged)
         ctx.counted = _acquire_sinks(ctx, params)
         return logits
 
@@ -1579,14 +1684,14 @@ class HeadFn(torch.autograd.Function):
     def backward(ctx, dlogits):
         if ctx.keep is None:
             raise RuntimeError('HeadFn: backward ran a second time (its arena is released after the first)')
-        hd, arena, x, y, xm, ym, params, ragged = ctx.keep
+        hd, arena, x, y, xm, ym, params, ragged, x_ragged = ctx.keep
         dlogits = _f32c(dlogits)
         dx, dy = torch.empty_like(x), torch.empty_like(y)
         hd.dlogits, hd.sx.dx, hd.sy.dx = L.fptr(dlogits), L.fptr(dx), L.fptr(dy)
         L.check(L.lib().mmnas_head_bwd(C.byref(hd), L.stream()))
         ctx.keep = None
         _release_sinks(ctx, params)
-        return dx, dy, None, None, None, None, None
+        return dx, dy, None, None, None, None, None, None
 
 
 def head_record(att_x, att_y, ln, proj, training):
