@@ -36,21 +36,6 @@ __device__ __forceinline__ float wave_sum(float v) {
   v += dpp_move<0x143, 0xc>(0.f, v);   // row_bcast:31 into rows 2 and 3
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
-// The coefficient of the std term of every hand-written LayerNorm backward (rowops.hip: ln_bwd_kernel and its copies):
-// sgc / (n1 * sd * sden^2), n1 = d - 1, sden = sd + eps, inv = 1 / sden, rn1 = 1 / n1 (row-invariant).  Two edges:
-//   sd == 0 (a constant row): 0 -- the reference's autograd masks std's backward to 0 there, so dx = (g - mean(g)) / eps;
-//     the plain quotient is 0 / 0.
-//   the denominator overflows (sd above ~5e11): sgc * inv^3 / n1 -- sd + eps == sd there, so 1 / sd == inv; the plain
-//     quotient is sgc / inf = 0 where the term is as large as the first one.
-// The edges select the OPERANDS of the one quotient (0 / 1, big / 1), so the division stays unconditional and an ordinary
-// row's quotient is the plain one.
-__device__ __forceinline__ float ln_bwd_k2(float sgc, float n1, float rn1, float sd, float sden, float inv) {
-  const float den = n1 * sd * sden * sden;
-  const float big = ((sgc * inv) * inv) * (inv * rn1);
-  const bool live = sd > 0.f, plain = live && den < __builtin_inff();
-  const float num = plain ? sgc : (live ? big : 0.f);
-  return num / (plain ? den : 1.f);
-}
 __device__ __forceinline__ float wave_max(float v) {
   constexpr float NI = -__builtin_inff();
   v = fmaxf(v, dpp_move<0xB1, 0xf>(NI, v));

@@ -11,6 +11,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "common.h"
+#include "ln_rows.h"
 
 namespace mmnas {
 
@@ -149,37 +150,6 @@ struct NodeMixArgs {
 };
 
 template <int NV>
-__device__ __forceinline__ void node_ln_row(float4 (&v)[NV], const float* __restrict__ a, const float* __restrict__ b, int lane, int d,
-                                            float eps) {
-  // (the arithmetic of ln_fwd_kernel, rowops.hip, operation for operation)
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < NV; ++i) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-  const float mean = wave_sum(s) / (float)d;
-  float ss = 0.f;
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int c = (lane + 64 * i) * 4;
-    if (c < d) {
-      v[i].x -= mean; v[i].y -= mean; v[i].z -= mean; v[i].w -= mean;
-      ss += (v[i].x * v[i].x + v[i].y * v[i].y) + (v[i].z * v[i].z + v[i].w * v[i].w);
-    }
-  }
-  const float sd = sqrtf(wave_sum(ss) / (float)(d - 1));
-  const float inv = 1.0f / (sd + eps);
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int c = (lane + 64 * i) * 4;
-    if (c < d) {
-      const float4 av = *reinterpret_cast<const float4*>(a + c);
-      const float4 bv = *reinterpret_cast<const float4*>(b + c);
-      v[i].x = av.x * v[i].x * inv + bv.x; v[i].y = av.y * v[i].y * inv + bv.y;
-      v[i].z = av.z * v[i].z * inv + bv.z; v[i].w = av.w * v[i].w * inv + bv.w;
-    }
-  }
-}
-
-template <int NV>
 __global__ void __launch_bounds__(256) node_mix_fwd_kernel(NodeMixArgs p, const float* __restrict__ gate, float* __restrict__ out,
                                                            int M, int d, float eps) {
   const int lane = threadIdx.x & 63;
@@ -202,7 +172,7 @@ __global__ void __launch_bounds__(256) node_mix_fwd_kernel(NodeMixArgs p, const 
 #pragma unroll
   for (int j = 0; j < MAXC; ++j)
     if (j < p.n && p.z[j]) {
-      if (p.a[j]) node_ln_row<NV>(v[j], p.a[j], p.b[j], lane, d, eps);
+      if (p.a[j]) ln_row_apply<NV>(v[j], p.a[j], p.b[j], lane, d, eps);
       const float g = gate[j];
 #pragma unroll
       for (int i = 0; i < NV; ++i) { acc[i].x += g * v[j][i].x; acc[i].y += g * v[j][i].y; acc[i].z += g * v[j][i].z; acc[i].w += g * v[j][i].w; }
@@ -220,8 +190,9 @@ __global__ void __launch_bounds__(256) node_mix_fwd_kernel(NodeMixArgs p, const 
 // for the gate's inner product, and d_active = gate[active] * dout would only be written to be read back by the candidate's
 // own ln_bwd launch (8 us + a launch boundary per node of the architecture step).  With LNB the kernel writes dz (gradient
 // wrt z_active), dt (the same behind the candidate's output dropout, replayed; NULL: none) and leaves the LayerNorm
-// parameter partials [workgroup][3][d] (dln_a, dln_b, column sums of dt) exactly as ln_bwd_kernel (rowops.hip) does -- the
-// same arithmetic operation for operation, the same row -> workgroup map (<= 512 workgroups) -- and d_active is not written.
+// parameter partials [workgroup][3][d] (dln_a, dln_b, column sums of dt) as ln_bwd_kernel (rowops.hip) does -- the same
+// expressions (written out here: the last bit differs between the two, ln_rows.h), the same hand-off, the same row -> workgroup
+// map (<= 512 workgroups) -- and d_active is not written.
 template <int NV, bool LNB>
 __global__ void __launch_bounds__(256) node_mix_bwd_kernel(NodeMixArgs p, const float* __restrict__ gate, const float* __restrict__ dout,
                                                            float* __restrict__ d_active, int active, float* __restrict__ part,
@@ -330,7 +301,7 @@ __global__ void __launch_bounds__(256) node_mix_bwd_kernel(NodeMixArgs p, const 
           }
           continue;
         }
-        if (p.a[j]) node_ln_row<NV>(v[j], p.a[j], p.b[j], lane, d, eps);
+        if (p.a[j]) ln_row_apply<NV>(v[j], p.a[j], p.b[j], lane, d, eps);
 #pragma unroll
         for (int i = 0; i < NV; ++i)
           s[j] += (g4[i].x * v[j][i].x + g4[i].y * v[j][i].y) + (g4[i].z * v[j][i].z + g4[i].w * v[j][i].w);

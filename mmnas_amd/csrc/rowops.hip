@@ -3,6 +3,7 @@
 // sums, the activation registry entries (modules.py:96-119, ops_adapter.py:25-29) and nn.GLU.
 // All are HBM-bound: one pass over the data, 16-byte accesses, one wave per row.
 #include "common.h"
+#include "ln_rows.h"
 
 namespace mmnas {
 
@@ -53,7 +54,7 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(const float* __restrict__ x
 // ---------------------------------------------------------------- LayerNorm backward
 // dx = (g - mean(g))/s - c * sum(g*c) / ((n-1) * sd * s^2),  g = dy*a, c = x-mean, s = sd+eps
 // (pinned by oracle.layer_norm_backward against the reference's autograd).  The second term's coefficient
-// is ln_bwd_k2 (common.h): 0 on a constant row, overflow-safe on huge ones; tests/test_ln_rows_gpu.py.
+// is ln_bwd_k2 (ln_rows.h): 0 on a constant row, overflow-safe on huge ones; tests/test_ln_rows_gpu.py.
 template <int NV>
 __global__ void __launch_bounds__(256) ln_bwd_kernel(const float* __restrict__ x, const float* __restrict__ a,
                                                      const float* __restrict__ dy, float* __restrict__ dx,

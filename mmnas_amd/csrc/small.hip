@@ -19,6 +19,7 @@
 // writes it, so either backward may follow.
 #include <string.h>
 #include "common.h"
+#include "ln_rows.h"
 
 namespace mmnas {
 

@@ -14,6 +14,7 @@
 //     same bits on every call.
 
 #include "common.h"
+#include "ln_rows.h"
 
 namespace mmnas {
 
