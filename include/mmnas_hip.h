@@ -510,7 +510,7 @@ int mmnas_set_rel_overlap(int on);
 * O [B*Sq, ldo] same column convention; lse [B,H,Sq,2] = (row max, 1/row sum) of each score row
  * (saved for backward instead of the map).  dropout idx = ((b*H+h)*Sq+q)*Sk+k.
  * Limits: dh in {16,32,64,128,256}; B*H*Sq*Sk < 2^32 (the dropout / bias index is 32-bit); row strides multiples of 4
- * floats, Q / K / V 16-byte aligned; packed rows (q_off / k_off) at dh = 64 with Sq, Sk <= 128.  No limit on the key count: up
+ * floats, Q / K / V 16-byte aligned; packed rows (q_off / k_off) at every dh with Sq, Sk <= 128.  No limit on the key count: up
  * to 256 keys the forward holds a query block's score row in registers, beyond it (or from MMNAS_MHA_STREAM_MINK keys on,
  * dense rows) it streams the keys in blocks of 128 with a running maximum and sum -- the same lse, the same dropout mask.
  * bwd recomputes P from (Q,K,lse): dQ,dK,dV (same layouts as Q,K,V) are overwritten;
@@ -530,11 +530,13 @@ typedef struct mmnas_mha_desc {
   float* dQ; float* dK; float* dV;
   float* dbiasT;           /* [B,H,Sk,Sq] or NULL */
   float* delta;            /* scratch [B,H,Sq] */
-  /* PACKED rows (ragged batches without their padding rows; d_h = 64, Sq, Sk <= 128): q_off / k_off = [B+1] device prefix
+  /* PACKED rows (ragged batches without their padding rows; every d_h, Sq, Sk <= 128): q_off / k_off = [B+1] device prefix
    * offsets -- batch b owns rows q_off[b] .. q_off[b+1] of Q / O / dO / dQ (k_off: of K / V / dK / dV), Sq / Sk are the
    * maximum lengths (strides of lse / delta / biasT, which keep their padded [B,H,...] layout).  Packed keys carry no
    * padding, so no mask goes with k_off.  The reference masks padded keys with -1e9 (modules.py:195-196): their
-   * probability is exactly 0 in fp32, so leaving them out changes nothing.  NULL = dense rows b * Sq + q. */
+   * probability is exactly 0 in fp32, so leaving them out changes nothing.  NULL = dense rows b * Sq + q.  d_h = 64 runs
+   * the fused / bf16-pipe backward (dK / dV 16-byte aligned), the other head sizes the query-owner + key-owner pair; of
+   * dbiasT only a sequence's n_k x n_q corner is written. */
   const int* q_off; const int* k_off;
 } mmnas_mha_desc;
 
@@ -715,7 +717,7 @@ typedef struct mmnas_chain {
    * The padding tokens of the reference's language stream follow the valid ones, are masked as keys in every encoder
    * self-attention and every guided attention and dropped by AttFlat's mask (hygr_vqa.py:113-122, modules.py:78-84,195-196):
    * no logit and no parameter gradient depends on them -- the argument of y_off.  Needs 0 < Nx <= B * Sx, Sx <= 128 (with a
-   * guided operator also Sy <= 128: the packed attention cores), a single stream and no encoder operator with MMNAS_F_REL,
+   * guided operator also Sy <= 128: the packed attention cores, at any head size), a single stream and no encoder operator with MMNAS_F_REL,
    * else MMNAS_E_ARG.  (Appended: a zero-initialised descriptor of a caller built against the shorter struct must be
    * rebuilt.) */
   const int* x_off;

@@ -589,8 +589,33 @@ __global__ void mha_delta_kernel(const float* __restrict__ dO, const float* __re
   }
 }
 
+// PACKED query rows: walks (b, q < n_b, h) over the padded index space, reads row qoff[b] + q, writes the padded [B,H,SqS] layout
+// (the entries of q >= n_b stay undefined: no kernel reads them).
+__global__ void mha_delta_packed_kernel(const float* __restrict__ dO, const float* __restrict__ O, float* __restrict__ delta,
+                                        const int* __restrict__ qoff, int B, int H, int SqS, int dh, int ldo) {
+  const long n = (long)B * SqS * H;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const int h = (int)(i % H);
+    const long bq = i / H;  // b*SqS + q
+    const int b = (int)(bq / SqS), q = (int)(bq - (long)b * SqS);
+    const int o = qoff[b];
+    if (q >= qoff[b + 1] - o) continue;
+    const long row = (long)o + q;
+    const float4* a = reinterpret_cast<const float4*>(dO + row * ldo + h * dh);
+    const float4* y4 = reinterpret_cast<const float4*>(O + row * ldo + h * dh);
+    float s = 0.f;
+    for (int j = 0; j < dh / 4; ++j) {
+      const float4 x = a[j], y = y4[j];
+      s += (x.x * y.x + x.y * y.y) + (x.z * y.z + x.w * y.w);
+    }
+    delta[((size_t)b * H + h) * SqS + q] = s;
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // backward, query-owner: dQ (head-dim chunk oc) and dZ -> dbiasT.
+// Packed rows (q_off / k_off) as in mha_fwd_body: a runtime, workgroup-uniform test on the pointers; SqS / SkS stay the strides
+// of stats / delta / bias / mask / the dropout index, Sq / Sk and the row bases are this sequence's own.
 // grid (ceil(Sq / (32 NW)), H * nch, B); keys swept in blocks of 32 NKC.
 // ------------------------------------------------------------------------------------------
 template <int DHC, int NKC, int NW>
@@ -604,21 +629,26 @@ __global__ void __launch_bounds__(64 * NW, (NKC <= 2 && NW == 4) ? 2 : 1) mha_bw
   __shared__ __attribute__((aligned(16))) float Vs[KB * LD];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l31 = lane & 31, hh = lane >> 5;
   const int b = blockIdx.z, h = blockIdx.y % p.H, oc = blockIdx.y / p.H, q0 = blockIdx.x * 32 * NW;
-  const int Sq = p.Sq, Sk = p.Sk;
+  const int SqS = p.Sq, SkS = p.Sk;   // strides of the per-(batch, head) arrays; the lengths of this batch element:
+  int Sq = p.Sq, Sk = p.Sk;
+  int qrow0 = b * p.Sq, krow0 = b * p.Sk;   // (first row of this batch element: 32-bit, as the dense row index b * S + r always was here)
+  if (p.qoff) { const int o = p.qoff[b]; Sq = p.qoff[b + 1] - o; qrow0 = o; }
+  if (p.koff) { const int o = p.koff[b]; Sk = p.koff[b + 1] - o; krow0 = o; }
+  if (q0 >= Sq) return;   // (packed rows: this query block lies behind the sequence's end; workgroup-uniform, before any barrier)
   const bool active = q0 + 32 * w < Sq;
   const int qi = q0 + 32 * w + l31;
   const bool qok = qi < Sq;
   const size_t bh = (size_t)b * p.H + h;
   float m = 0.f, inv = 0.f, del = 0.f;
   if (qok) {
-    m = p.stats[(bh * Sq + qi) * 2];
-    inv = p.stats[(bh * Sq + qi) * 2 + 1];
-    if (p.nch > 1) del = p.delta[bh * Sq + qi];   // (one head-dim chunk: computed below from the fragments)
+    m = p.stats[(bh * SqS + qi) * 2];
+    inv = p.stats[(bh * SqS + qi) * 2 + 1];
+    if (p.nch > 1) del = p.delta[bh * SqS + qi];   // (one head-dim chunk: computed below from the fragments)
   }
   float4 qfr[NS], gfr[NS];   // B operands of S^T = K Q^T and dA^T = V dO^T for head-dim chunk c
   auto load_frags = [&](int c) {
     const int co = h * p.dh + c * DHC + 4 * hh;
-    const size_t row = (size_t)b * Sq + (qok ? qi : Sq - 1);   // clamped: no branch around the loads
+    const size_t row = (size_t)(qrow0 + (qok ? qi : Sq - 1));   // clamped inside this sequence's rows: no branch around the loads
     const float* qrow = p.Q + row * p.ldq + co;
     const float* grow = p.dO + row * p.ldo + co;
 #pragma unroll
@@ -635,7 +665,7 @@ __global__ void __launch_bounds__(64 * NW, (NKC <= 2 && NW == 4) ? 2 : 1) mha_bw
     // delta[b,h,q] = sum_j dO[q,j] O[q,j] (= sum_k dA[q,k] A[q,k]) from this lane's half row, the other half-wave
     // holds the other half; written for the dK/dV kernel that follows on the stream (replaces a separate launch)
     load_frags(0);
-    const float* orow = p.O + ((size_t)b * Sq + (qok ? qi : Sq - 1)) * p.ldo + h * p.dh + 4 * hh;
+    const float* orow = p.O + (size_t)(qrow0 + (qok ? qi : Sq - 1)) * p.ldo + h * p.dh + 4 * hh;
     float part = 0.f;
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
@@ -644,7 +674,7 @@ __global__ void __launch_bounds__(64 * NW, (NKC <= 2 && NW == 4) ? 2 : 1) mha_bw
     }
     part += __shfl_xor(part, 32, 64);
     del = qok ? part : 0.f;
-    if (qok && hh == 0) p.delta[bh * Sq + qi] = del;
+    if (qok && hh == 0) p.delta[bh * SqS + qi] = del;
   }
   f32x16 dq[JC];
 #pragma unroll
@@ -662,8 +692,8 @@ __global__ void __launch_bounds__(64 * NW, (NKC <= 2 && NW == 4) ? 2 : 1) mha_bw
       __syncthreads();
       const int co = h * p.dh + c * DHC;
       if (p.nch > 1) load_frags(c);
-      load_tiles2<KB, KB, DHC, NT>(Ks, p.K + (size_t)(b * Sk + kb) * p.ldk + co, Sk - kb, p.ldk,
-                                   Vs, p.V + (size_t)(b * Sk + kb) * p.ldv + co, Sk - kb, p.ldv, tid);
+      load_tiles2<KB, KB, DHC, NT>(Ks, p.K + (size_t)(krow0 + kb) * p.ldk + co, Sk - kb, p.ldk,
+                                   Vs, p.V + (size_t)(krow0 + kb) * p.ldv + co, Sk - kb, p.ldv, tid);
       __syncthreads();
       if (active) {
 #pragma unroll
@@ -691,8 +721,8 @@ __global__ void __launch_bounds__(64 * NW, (NKC <= 2 && NW == 4) ? 2 : 1) mha_bw
 #pragma unroll
       for (int r = 0; r < 16; ++r) {  // batched, branch-free operand fetch (clamped indices)
         const int key = min(kb + 32 * kc + acc_row(r, hh), Sk - 1);
-        bias[r] = has_bias ? p.biasT[(bh * Sk + key) * Sq + qic] : 0.f;
-        mk[r] = has_mask ? (float)p.mask[(size_t)b * Sk + key] : 0.f;
+        bias[r] = has_bias ? p.biasT[(bh * SkS + key) * SqS + qic] : 0.f;
+        mk[r] = has_mask ? (float)p.mask[(size_t)b * SkS + key] : 0.f;
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -702,15 +732,15 @@ __global__ void __launch_bounds__(64 * NW, (NKC <= 2 && NW == 4) ? 2 : 1) mha_bw
         float v = acc[kc][r] * p.scale + bias[r];
         if (masked) v = -1e9f;
         const float pr = __expf(v - m) * inv;
-        const float dm = has_drop ? drop_mult(p.drop, (uint32_t)((bh * Sq + qi) * Sk + key)) : 1.f;
+        const float dm = has_drop ? drop_mult(p.drop, (uint32_t)((bh * SqS + qi) * SkS + key)) : 1.f;
         const float dz = (ok && !masked) ? pr * (dacc[kc][r] * dm - del) : 0.f;
-        if (put_dbias && ok) p.dbiasT[(bh * Sk + key) * Sq + qi] = dz;
+        if (put_dbias && ok) p.dbiasT[(bh * SkS + key) * SqS + qi] = dz;
         acc[kc][r] = dz * p.scale;
       }
     }
     if (p.nch > 1) {
       __syncthreads();
-      load_tile<KB, DHC, NT>(Ks, p.K + (size_t)(b * Sk + kb) * p.ldk + h * p.dh + oc * DHC, Sk - kb, p.ldk, tid);
+      load_tile<KB, DHC, NT>(Ks, p.K + (size_t)(krow0 + kb) * p.ldk + h * p.dh + oc * DHC, Sk - kb, p.ldk, tid);
       __syncthreads();
     }
     if (active) {
@@ -735,7 +765,7 @@ __global__ void __launch_bounds__(64 * NW, (NKC <= 2 && NW == 4) ? 2 : 1) mha_bw
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int q = q0 + 32 * w + acc_row(r, hh);
-          if (q < Sq) p.dQ[(size_t)(b * Sq + q) * p.ldq + h * p.dh + oc * DHC + col] = dq[jc][r];
+          if (q < Sq) p.dQ[(size_t)(qrow0 + q) * p.ldq + h * p.dh + oc * DHC + col] = dq[jc][r];
         }
       }
     }
@@ -769,11 +799,16 @@ __global__ void __launch_bounds__(64 * NW * QS, (NW == 4 && QS == 1) ? 2 : 1) mh
   float* sDel = sDelAll + qs * 32;
   const int lane = tid & 63, w = tid >> 6, l31 = lane & 31, hh = lane >> 5;
   const int b = blockIdx.z, h = blockIdx.y % p.H, oc = blockIdx.y / p.H, k0 = blockIdx.x * 32 * NW;
-  const int Sq = p.Sq, Sk = p.Sk;
+  const int SqS = p.Sq, SkS = p.Sk;   // strides of the per-(batch, head) arrays; the lengths of this batch element:
+  int Sq = p.Sq, Sk = p.Sk;
+  int qrow0 = b * p.Sq, krow0 = b * p.Sk;   // (first row of this batch element: 32-bit, as the dense row index b * S + r always was here)
+  if (p.qoff) { const int o = p.qoff[b]; Sq = p.qoff[b + 1] - o; qrow0 = o; }
+  if (p.koff) { const int o = p.koff[b]; Sk = p.koff[b + 1] - o; krow0 = o; }
+  if (k0 >= Sk) return;   // (packed rows: this key block lies behind the sequence's end; the same for all QS groups, before any barrier)
   const bool active = k0 + 32 * w < Sk;
   const int key = k0 + 32 * w + l31;
   const bool kok = key < Sk;
-  const bool masked = kok && p.mask && p.mask[(size_t)b * Sk + key];
+  const bool masked = kok && p.mask && p.mask[(size_t)b * SkS + key];
   const size_t bh = (size_t)b * p.H + h;
   f32x16 dk[JC], dv[JC];
 #pragma unroll
@@ -783,7 +818,7 @@ __global__ void __launch_bounds__(64 * NW * QS, (NW == 4 && QS == 1) ? 2 : 1) mh
   float4 kfr[NS], vfr[NS];
   auto load_frags = [&](int c) {
     const int co = h * p.dh + c * DHC + 4 * hh;
-    const size_t row = (size_t)b * Sk + (kok ? key : Sk - 1);   // clamped: no branch around the loads
+    const size_t row = (size_t)(krow0 + (kok ? key : Sk - 1));   // clamped inside this sequence's rows: no branch around the loads
     const float* krow = p.K + row * p.ldk + co;
     const float* vrow = p.V + row * p.ldv + co;
 #pragma unroll
@@ -808,15 +843,15 @@ __global__ void __launch_bounds__(64 * NW * QS, (NW == 4 && QS == 1) ? 2 : 1) mh
       __syncthreads();
       const int co = h * p.dh + c * DHC;
       const int qcl = qc < Sq ? qc : 0;   // (a block beyond Sq: valid addresses, zero rows)
-      load_tiles2<32, 32, DHC, NT>(Qs, p.Q + (size_t)(b * Sq + qcl) * p.ldq + co, Sq - qc, p.ldq,
-                                   Gs, p.dO + (size_t)(b * Sq + qcl) * p.ldo + co, Sq - qc, p.ldo, tid);
+      load_tiles2<32, 32, DHC, NT>(Qs, p.Q + (size_t)(qrow0 + qcl) * p.ldq + co, Sq - qc, p.ldq,
+                                   Gs, p.dO + (size_t)(qrow0 + qcl) * p.ldo + co, Sq - qc, p.ldo, tid);
       if (p.nch > 1 || qc0 == 0) load_frags(c);
       if (c == 0 && tid < 32) {
         const int q = qc + tid;
         const bool ok = q < Sq;
-        sM[tid] = ok ? p.stats[(bh * Sq + q) * 2] : 0.f;
-        sInv[tid] = ok ? p.stats[(bh * Sq + q) * 2 + 1] : 0.f;
-        sDel[tid] = ok ? p.delta[bh * Sq + q] : 0.f;
+        sM[tid] = ok ? p.stats[(bh * SqS + q) * 2] : 0.f;
+        sInv[tid] = ok ? p.stats[(bh * SqS + q) * 2 + 1] : 0.f;
+        sDel[tid] = ok ? p.delta[bh * SqS + q] : 0.f;
       }
       __syncthreads();
       if (active) {
@@ -840,7 +875,7 @@ __global__ void __launch_bounds__(64 * NW * QS, (NW == 4 && QS == 1) ? 2 : 1) mh
 #pragma unroll
       for (int r = 0; r < 16; ++r) {  // batched, branch-free bias fetch (clamped indices)
         const int q = min(qc + acc_row(r, hh), Sq - 1);
-        bias[r] = has_bias ? p.biasT[(bh * Sk + keyc) * Sq + q] : 0.f;
+        bias[r] = has_bias ? p.biasT[(bh * SkS + keyc) * SqS + q] : 0.f;
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -849,7 +884,7 @@ __global__ void __launch_bounds__(64 * NW * QS, (NW == 4 && QS == 1) ? 2 : 1) mh
         float v = acc[r] * p.scale + bias[r];
         if (masked) v = -1e9f;
         const float pr = __expf(v - sM[ql]) * sInv[ql];
-        const float dm = has_drop ? drop_mult(p.drop, (uint32_t)((bh * Sq + q) * Sk + key)) : 1.f;
+        const float dm = has_drop ? drop_mult(p.drop, (uint32_t)((bh * SqS + q) * SkS + key)) : 1.f;
         acc[r] = ok ? pr * dm : 0.f;
         dacc[r] = (ok && !masked) ? pr * (dacc[r] * dm - sDel[ql]) * p.scale : 0.f;
       }
@@ -858,8 +893,8 @@ __global__ void __launch_bounds__(64 * NW * QS, (NW == 4 && QS == 1) ? 2 : 1) mh
       __syncthreads();
       const int co = h * p.dh + oc * DHC;
       const int qcl = qc < Sq ? qc : 0;
-      load_tiles2<32, 32, DHC, NT>(Qs, p.Q + (size_t)(b * Sq + qcl) * p.ldq + co, Sq - qc, p.ldq,
-                                   Gs, p.dO + (size_t)(b * Sq + qcl) * p.ldo + co, Sq - qc, p.ldo, tid);
+      load_tiles2<32, 32, DHC, NT>(Qs, p.Q + (size_t)(qrow0 + qcl) * p.ldq + co, Sq - qc, p.ldq,
+                                   Gs, p.dO + (size_t)(qrow0 + qcl) * p.ldo + co, Sq - qc, p.ldo, tid);
       __syncthreads();
     }
     if (active) {
@@ -912,8 +947,8 @@ __global__ void __launch_bounds__(64 * NW * QS, (NW == 4 && QS == 1) ? 2 : 1) mh
         for (int r = 0; r < 16; ++r) {
           const int kr = k0 + 32 * w + acc_row(r, hh);
           if (kr < Sk) {
-            p.dK[(size_t)(b * Sk + kr) * p.ldk + h * p.dh + oc * DHC + col] = dk[jc][r];
-            p.dV[(size_t)(b * Sk + kr) * p.ldv + h * p.dh + oc * DHC + col] = dv[jc][r];
+            p.dK[(size_t)(krow0 + kr) * p.ldk + h * p.dh + oc * DHC + col] = dk[jc][r];
+            p.dV[(size_t)(krow0 + kr) * p.ldv + h * p.dh + oc * DHC + col] = dv[jc][r];
           }
         }
       }
@@ -1233,7 +1268,7 @@ static int fill(const mmnas_mha_desc* d, MhaK& k, bool bwd) {
   k.dO = d->dO; k.dQ = d->dQ; k.dK = d->dK; k.dV = d->dV; k.dbiasT = d->dbiasT; k.delta = d->delta;
   k.qoff = d->q_off; k.koff = d->k_off;
   if (k.qoff || k.koff) {
-    MMNAS_REQUIRE(d->dh == 64 && d->Sq <= 128 && d->Sk <= 128, MMNAS_E_SHAPE, "mha: packed rows (q_off / k_off) need d_h = 64 and at most 128 queries / keys per sequence (Sq=%d Sk=%d dh=%d)", d->Sq, d->Sk, d->dh);
+    MMNAS_REQUIRE(d->Sq <= 128 && d->Sk <= 128, MMNAS_E_SHAPE, "mha: packed rows (q_off / k_off) need at most 128 queries / keys per sequence (Sq=%d Sk=%d)", d->Sq, d->Sk);
     MMNAS_REQUIRE(!(k.koff && d->mask), MMNAS_E_ARG, "mha: packed keys carry no padding: no mask with k_off");
   }
   if (bwd) {
@@ -1407,7 +1442,8 @@ extern "C" int mmnas_mha_core_bwd(const mmnas_mha_desc* d, void* stream) {
                4.0 * ((double)k.B * k.H * k.dh * (4.0 * k.Sq + 4.0 * k.Sk) + (k.biasT ? 2.0 * bhqk : 0.0)), st);
   const bool fused_on = sw::mha_bwd_fused.get() != 0;
   const bool packed = k.qoff || k.koff;
-  if (packed) MMNAS_REQUIRE((((uintptr_t)k.dK | (uintptr_t)k.dV) & 15) == 0, MMNAS_E_ARG, "mha_bwd: dK / dV alignment (packed rows run the fused kernel only)");
+  // (packed rows at d_h = 64 run the fused / bf16 kernels whatever MMNAS_MHA_BWD_FUSED says; the other head sizes the general pair below)
+  if (packed && k.dh == 64) MMNAS_REQUIRE((((uintptr_t)k.dK | (uintptr_t)k.dV) & 15) == 0, MMNAS_E_ARG, "mha_bwd: dK / dV alignment (packed rows at d_h = 64 run the fused kernels)");
   if ((fused_on || packed) && k.dh == 64 && k.Sq <= 128 && k.Sk <= 128 && (((uintptr_t)k.dK | (uintptr_t)k.dV) & 15) == 0) {
     k.nch = 1;
     // 65..128 keys (the image stream): all five products on the bf16 pipe as exactly split operands (attention_bwd16.hip)
@@ -1431,8 +1467,10 @@ extern "C" int mmnas_mha_core_bwd(const mmnas_mha_desc* d, void* stream) {
     const long n = (long)k.B * k.Sq * k.H;
     int blocks = (int)((n + 255) / 256);
     if (blocks > 2048) blocks = 2048;
-    MMNAS_LAUNCH(mha_delta_kernel, dim3(blocks), dim3(256), 0, st, k.dO, (const float*)d->O, k.delta, k.B, k.H,
-                       k.Sq, k.dh, k.ldo);
+    if (k.qoff) MMNAS_LAUNCH(mha_delta_packed_kernel, dim3(blocks), dim3(256), 0, st, k.dO, (const float*)d->O, k.delta, k.qoff, k.B, k.H,
+                             k.Sq, k.dh, k.ldo);
+    else MMNAS_LAUNCH(mha_delta_kernel, dim3(blocks), dim3(256), 0, st, k.dO, (const float*)d->O, k.delta, k.B, k.H,
+                      k.Sq, k.dh, k.ldo);
   }
   if (k.dh >= 64) { k.nch = k.dh / 64; launch_bwd<64>(k, st); }
   else if (k.dh == 32) { k.nch = 1; launch_bwd<32>(k, st); }

@@ -681,11 +681,12 @@ static int chain_check(const mmnas_chain* c, const char* who) {
     if (o.kind == MMNAS_CHAIN_ATT && !(o.att.flags & MMNAS_F_SELF))
       MMNAS_REQUIRE(o.on_y, MMNAS_E_ARG, "%s: operator %d: guided attention needs the decoder stream", who, i);
     if (c->x_off && o.kind == MMNAS_CHAIN_ATT) {
-      // the token relations stay a padded [B,Sx,Sx,C] tensor nobody tiles for packed rows; the packed cores: heads of 64, <= 128 queries
+      // the token relations stay a padded [B,Sx,Sx,C] tensor nobody tiles for packed rows; the packed cores: every head size,
+      // <= 128 queries / keys per sequence
       MMNAS_REQUIRE(o.on_y || !(o.att.flags & MMNAS_F_REL), MMNAS_E_ARG, "%s: operator %d: ragged language stream: no encoder operator with a relation bias", who, i);
       if (!o.on_y || !(o.att.flags & MMNAS_F_SELF))
-        MMNAS_REQUIRE(o.att.dh == 64 && (!o.on_y || c->Sy <= 128), MMNAS_E_ARG,
-                      "%s: operator %d: ragged language stream: packed keys need heads of 64 (dh=%d) and Sy=%d <= 128", who, i, o.att.dh, c->Sy);
+        MMNAS_REQUIRE(!o.on_y || c->Sy <= 128, MMNAS_E_ARG,
+                      "%s: operator %d: ragged language stream: packed keys need Sy=%d <= 128 queries", who, i, c->Sy);
     }
   }
   if (c->mixed) {

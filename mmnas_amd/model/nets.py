@@ -82,7 +82,7 @@ class _Backbone(nn.Module):
         when any of that does not hold: the per-operator path below serves every other case.
         x_ragged (ops.Ragged; ops.set_unpad_x): `x` holds the PACKED rows of a ragged language stream and comes back packed.
         None as well when an encoder operator carries a relation bias (the token relations stay a padded tensor: the caller
-        keeps the trimmed dense stream) or an operator's heads are not the packed attention cores' 64."""
+        keeps the trimmed dense stream).  The packed attention cores serve every head size of the registry."""
         from .modules import FeedForward, FeedForward_deep, GuidedAtt, RelSelfAtt, SelfAtt
         if not (ops.chain_enabled() and x.is_cuda and x.dtype == torch.float32 and y.dtype == torch.float32):
             return None
@@ -244,8 +244,6 @@ class _Backbone(nn.Module):
                     op_params[i] = [op_params[i][0]] + list(op_params[i][3:])
                 op_params[g0] = list(op_params[g0]) + extra
         if not records or len(records) > 128:
-            return None
-        if x_ragged is not None and any(r.kind == 0 and r.att.dh != 64 and not (r.on_y and r.att.flags & ops.L.F_SELF) for r in records):
             return None
         xr = x_rel_embed.raw if isinstance(x_rel_embed, RelHandle) else None
         yr = y_rel_embed.raw if isinstance(y_rel_embed, RelHandle) else None

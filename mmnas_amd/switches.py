@@ -85,6 +85,7 @@ LIB_PATH = _flag('MMNAS_LIB_PATH', None, 'string', 'doc', 'path of the shared li
 _flag('MMNAS_REFERENCE_ROOT', None, 'string', 'doc', "a checkout of the reference whose mmnas/ package is merged behind this repository's (mmnas/__init__.py)")
 _flag('MMNAS_PROF_DUMP', None, 'string', 'doc', 'file the native profiler appends one row per bracketed launch to (csrc/util.hip)')
 _flag('MMNAS_LN_ROWS_STATS', None, 'string', 'doc', 'file tests/test_ln_rows_gpu.py writes the worst LayerNorm error per (kernel, row class, output) to (tests/ln_rows.py)')
+_flag('MMNAS_PACKED_HEADS_STATS', None, 'string', 'doc', 'file tests/test_ragged_heads_gpu.py writes the worst ragged-against-padded error per case to (heads of 16 / 32 / 128 / 256 on the ragged streams)')
 
 
 @contextlib.contextmanager
