@@ -134,6 +134,19 @@ int attflat_pool_bwd_packed(const float* probs, const float* x, const float* dpo
 constexpr int ADD_MANY_MAX = 24;
 int add_many(const float* const* srcs, int n, float* y, size_t count, hipStream_t st);
 
+// util.hip: Adam's scalar coefficients, the one way for every Adam entry (mmnas_adam_step, mmnas_alpha_full_step[_wd|_cost],
+// mmnas_alpha_two_step[_cost]).  decimal_of: a float coefficient as the caller wrote it -- the shortest decimal that rounds back
+// to the float, read as a double (0.999f -> 0.999).  adam_coef forms 1 - beta and the bias corrections in double from those
+// decimals, as torch.optim.Adam forms them from Python floats, and rounds each once to float: 1.f - 0.999f is 1.29e-5
+// (relative) away from 0.001, and with it exp_avg_sq from what torch keeps in its checkpoint.
+struct AdamCoef {
+  float c1;          // 1 - beta1^step
+  float c2s;         // sqrt(1 - beta2^step)
+  float omb1, omb2;  // 1 - beta1, 1 - beta2
+};
+double decimal_of(float x);
+AdamCoef adam_coef(float beta1, float beta2, int step);
+
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 }  // namespace mmnas

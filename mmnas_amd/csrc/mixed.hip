@@ -423,10 +423,10 @@ __device__ __forceinline__ void alpha_full_row(float* __restrict__ prob, const f
 // one thread per node (row): 'full'-mode architecture gradient + Adam
 __global__ void alpha_full_step_kernel(float* __restrict__ prob, const float* __restrict__ gate_grad, float* __restrict__ m,
                                        float* __restrict__ v, float* __restrict__ prob_grad, int rows, int width, float lr,
-                                       float b1, float b2, float eps, float c1, float c2s, float wd) {
+                                       float b1, float b2, float omb1, float omb2, float eps, float c1, float c2s, float wd) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= rows) return;
-  alpha_full_row<false>(prob, gate_grad, m, v, prob_grad, r, width, lr, b1, b2, 1.f - b1, 1.f - b2, eps, c1, c2s, wd, nullptr, 0.f);
+  alpha_full_row<false>(prob, gate_grad, m, v, prob_grad, r, width, lr, b1, b2, omb1, omb2, eps, c1, c2s, wd, nullptr, 0.f);
 }
 
 // the same with the expected-cost term: ONE workgroup of 256 threads walks the rows (alpha_cost_scale says why)
@@ -476,7 +476,7 @@ __device__ __forceinline__ void alpha_two_row(float* __restrict__ prob, const fl
     if (prob_grad) prob_grad[o] = grad;
     if (!(ai > -INFINITY)) continue;                        // padding column: stays -inf, its moments untouched
     if (wd != 0.f) grad += wd * ai;                         // torch Adam's weight_decay: p.grad itself stays as it is
-    const float mi = b1 * m[o] + omb1 * grad;               // omb = 1 - beta, formed on the host (see mmnas_alpha_two_step)
+    const float mi = b1 * m[o] + omb1 * grad;               // omb = 1 - beta, formed on the host (adam_coef)
     const float vi = b2 * v[o] + omb2 * grad * grad;
     m[o] = mi; v[o] = vi;
     a[i] = ai - (lr / c1) * mi / (sqrtf(vi) / c2s + eps);
@@ -564,28 +564,15 @@ extern "C" int mmnas_alpha_full_step_wd(float* prob, const float* gate_grad, flo
                                         void* stream) {
   MMNAS_REQUIRE(prob && gate_grad && m && v && step >= 1 && rows >= 0 && width >= 1, MMNAS_E_ARG, "mmnas_alpha_full_step / mmnas_alpha_full_step_wd: bad arguments");
   if (rows == 0) return MMNAS_OK;
-  const float c1 = 1.f - powf(beta1, (float)step);
-  const float c2s = sqrtf(1.f - powf(beta2, (float)step));
+  const AdamCoef k = adam_coef(beta1, beta2, step);
   MMNAS_LAUNCH(alpha_full_step_kernel, dim3(cdiv(rows, 64)), dim3(64), 0, (hipStream_t)stream, prob, gate_grad, m, v, prob_grad,
-               rows, width, lr, beta1, beta2, eps, c1, c2s, weight_decay);
+               rows, width, lr, beta1, beta2, k.omb1, k.omb2, eps, k.c1, k.c2s, weight_decay);
   return check_launch("alpha_full_step");
 }
 
 extern "C" int mmnas_alpha_full_step(float* prob, const float* gate_grad, float* m, float* v, float* prob_grad, int rows,
                                      int width, float lr, float beta1, float beta2, float eps, int step, void* stream) {
   return mmnas_alpha_full_step_wd(prob, gate_grad, m, v, prob_grad, rows, width, lr, beta1, beta2, eps, 0.f, step, stream);
-}
-
-// A float coefficient as the caller wrote it: the shortest decimal that rounds back to the float, read as a double
-// (0.999f -> 0.999).  1 - 0.999f is 1.3e-5 (relative) away from 0.001, and with it exp_avg_sq from what torch Adam -- which
-// forms 1 - beta2 and the bias corrections from Python floats -- keeps in its checkpoint.
-static double decimal_of(float x) {
-  char buf[40];
-  for (int digits = 1; digits <= 9; ++digits) {
-    snprintf(buf, sizeof(buf), "%.*g", digits, (double)x);
-    if (strtof(buf, nullptr) == x) break;
-  }
-  return strtod(buf, nullptr);
 }
 
 extern "C" int mmnas_alpha_two_step(float* prob, const float* gate_grad, float* m, float* v, float* prob_grad, int rows,
@@ -604,16 +591,13 @@ extern "C" int mmnas_alpha_two_step(float* prob, const float* gate_grad, float* 
     pa.ij[2 * r] = i;
     pa.ij[2 * r + 1] = j;
   }
-  const double b1 = decimal_of(beta1), b2 = decimal_of(beta2);
-  const float c1 = (float)(1.0 - pow(b1, (double)step));
-  const float c2s = (float)sqrt(1.0 - pow(b2, (double)step));
+  const AdamCoef k = adam_coef(beta1, beta2, step);
   MMNAS_LAUNCH(alpha_two_step_kernel, dim3(cdiv(rows, 64)), dim3(64), 0, (hipStream_t)stream, prob, gate_grad, m, v, prob_grad,
-               rows, width, lr, beta1, beta2, (float)(1.0 - b1), (float)(1.0 - b2), eps, c1, c2s, weight_decay, pa);
+               rows, width, lr, beta1, beta2, k.omb1, k.omb2, eps, k.c1, k.c2s, weight_decay, pa);
   return check_launch("alpha_two_step");
 }
 
-// The cost entries: what both check before anything else; the coefficients as mmnas_alpha_two_step forms them (in 'full' too:
-// float(1 - 0.999f) is 1.3e-5 away from 0.001, more than the entries' float64 checks allow exp_avg_sq).
+// The cost entries: what both check before anything else (the coefficients: adam_coef, as every Adam entry).
 static int alpha_cost_args(const char* who, const float* prob, const float* gate_grad, const float* m, const float* v,
                            const float* cost, int width, int min_width, float cost_weight, float cost_ref, int cost_form, int step) {
   MMNAS_REQUIRE(step >= 1 && width >= min_width, MMNAS_E_ARG, "%s: step=%d (>= 1) width=%d (>= %d)", who, step, width, min_width);
@@ -632,12 +616,10 @@ extern "C" int mmnas_alpha_full_step_cost(float* prob, const float* gate_grad, f
   MMNAS_REQUIRE(rows >= 0, MMNAS_E_ARG, "mmnas_alpha_full_step_cost: rows=%d", rows);
   const int rc = alpha_cost_args("mmnas_alpha_full_step_cost", prob, gate_grad, m, v, cost, width, 1, cost_weight, cost_ref, cost_form, step);
   if (rc != MMNAS_OK) return rc;
-  const double b1 = decimal_of(beta1), b2 = decimal_of(beta2);
-  const float c1 = (float)(1.0 - pow(b1, (double)step));
-  const float c2s = (float)sqrt(1.0 - pow(b2, (double)step));
+  const AdamCoef k = adam_coef(beta1, beta2, step);
   const AlphaCost ac{cost, stats, cost_weight, cost_ref, cost_form};
   MMNAS_LAUNCH(alpha_full_step_cost_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, prob, gate_grad, m, v, prob_grad, rows, width,
-               lr, beta1, beta2, (float)(1.0 - b1), (float)(1.0 - b2), eps, c1, c2s, weight_decay, ac);
+               lr, beta1, beta2, k.omb1, k.omb2, eps, k.c1, k.c2s, weight_decay, ac);
   return check_launch("alpha_full_step_cost");
 }
 
@@ -658,12 +640,10 @@ extern "C" int mmnas_alpha_two_step_cost(float* prob, const float* gate_grad, fl
     pa.ij[2 * r] = i;
     pa.ij[2 * r + 1] = j;
   }
-  const double b1 = decimal_of(beta1), b2 = decimal_of(beta2);
-  const float c1 = (float)(1.0 - pow(b1, (double)step));
-  const float c2s = (float)sqrt(1.0 - pow(b2, (double)step));
+  const AdamCoef k = adam_coef(beta1, beta2, step);
   const AlphaCost ac{cost, stats, cost_weight, cost_ref, cost_form};
   MMNAS_LAUNCH(alpha_two_step_cost_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, prob, gate_grad, m, v, prob_grad, rows, width,
-               lr, beta1, beta2, (float)(1.0 - b1), (float)(1.0 - b2), eps, c1, c2s, weight_decay, pa, ac);
+               lr, beta1, beta2, k.omb1, k.omb2, eps, k.c1, k.c2s, weight_decay, pa, ac);
   return check_launch("alpha_two_step_cost");
 }
 

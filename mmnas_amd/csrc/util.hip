@@ -107,6 +107,25 @@ static hipEvent_t get_event() {
 
 bool prof_enabled() { return prof::enabled; }
 
+double decimal_of(float x) {
+  char buf[40];
+  for (int digits = 1; digits <= 9; ++digits) {
+    snprintf(buf, sizeof(buf), "%.*g", digits, (double)x);
+    if (strtof(buf, nullptr) == x) break;
+  }
+  return strtod(buf, nullptr);
+}
+
+AdamCoef adam_coef(float beta1, float beta2, int step) {
+  const double b1 = decimal_of(beta1), b2 = decimal_of(beta2);
+  AdamCoef k;
+  k.c1 = (float)(1.0 - pow(b1, (double)step));
+  k.c2s = (float)sqrt(1.0 - pow(b2, (double)step));
+  k.omb1 = (float)(1.0 - b1);
+  k.omb2 = (float)(1.0 - b2);
+  return k;
+}
+
 struct ActiveScope { long idx; bool started; };
 static thread_local ActiveScope g_active = {-1, false};
 
@@ -212,16 +231,18 @@ __global__ void pack_args_kernel(PackArgs a, int nseg, size_t npieces, float* st
   pack_body(a.s, nseg, npieces, staging, scale, direction);
 }
 
+// omb1 / omb2 = 1 - beta, c1 / c2: all four formed on the host (adam_coef)
 __global__ void adam_kernel(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1,
-                            float b2, float eps, float wd, const float* sumsq, float max_norm, float c1, float c2) {
+                            float b2, float omb1, float omb2, float eps, float wd, const float* sumsq, float max_norm, float c1,
+                            float c2) {
   float gscale = 1.f;
   if (sumsq) gscale = fminf(1.f, max_norm / (sqrtf(*sumsq) + 1e-6f));
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     float gi = g[i] * gscale;
     float pi = p[i];
     if (wd != 0.f) gi += wd * pi;
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    const float mi = b1 * m[i] + omb1 * gi;
+    const float vi = b2 * v[i] + omb2 * gi * gi;
     m[i] = mi; v[i] = vi;
     // torch.optim.Adam: denom = sqrt(v)/sqrt(1-b2^t) + eps ; p -= lr/(1-b1^t) * m/denom
     p[i] = pi - (lr / c1) * mi / (sqrtf(vi) / c2 + eps);
@@ -231,25 +252,26 @@ __global__ void adam_kernel(float* p, const float* g, float* m, float* v, size_t
 // the same arithmetic on four consecutive elements per thread and pass: 16-byte loads / stores (the scalar form moved
 // 4 bytes per lane and instruction: 0.45 ms for the supernet's 37 M parameters where 1.04 GB of traffic is 0.21 ms at 5 TB/s)
 __device__ __forceinline__ void adam_one(float& pi, float gi, float& mi, float& vi, float gscale, float lr, float b1, float b2,
-                                         float eps, float wd, float c1, float c2) {
+                                         float omb1, float omb2, float eps, float wd, float c1, float c2) {
   gi *= gscale;
   if (wd != 0.f) gi += wd * pi;
-  mi = b1 * mi + (1.f - b1) * gi;
-  vi = b2 * vi + (1.f - b2) * gi * gi;
+  mi = b1 * mi + omb1 * gi;
+  vi = b2 * vi + omb2 * gi * gi;
   pi = pi - (lr / c1) * mi / (sqrtf(vi) / c2 + eps);
 }
 __global__ void __launch_bounds__(256) adam4_kernel(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ m,
-                                                    float4* __restrict__ v, size_t n4, float lr, float b1, float b2, float eps,
-                                                    float wd, const float* sumsq, float max_norm, float c1, float c2) {
+                                                    float4* __restrict__ v, size_t n4, float lr, float b1, float b2, float omb1,
+                                                    float omb2, float eps, float wd, const float* sumsq, float max_norm, float c1,
+                                                    float c2) {
   float gscale = 1.f;
   if (sumsq) gscale = fminf(1.f, max_norm / (sqrtf(*sumsq) + 1e-6f));
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
     float4 pi = p[i], mi = m[i], vi = v[i];
     const float4 gi = g[i];
-    adam_one(pi.x, gi.x, mi.x, vi.x, gscale, lr, b1, b2, eps, wd, c1, c2);
-    adam_one(pi.y, gi.y, mi.y, vi.y, gscale, lr, b1, b2, eps, wd, c1, c2);
-    adam_one(pi.z, gi.z, mi.z, vi.z, gscale, lr, b1, b2, eps, wd, c1, c2);
-    adam_one(pi.w, gi.w, mi.w, vi.w, gscale, lr, b1, b2, eps, wd, c1, c2);
+    adam_one(pi.x, gi.x, mi.x, vi.x, gscale, lr, b1, b2, omb1, omb2, eps, wd, c1, c2);
+    adam_one(pi.y, gi.y, mi.y, vi.y, gscale, lr, b1, b2, omb1, omb2, eps, wd, c1, c2);
+    adam_one(pi.z, gi.z, mi.z, vi.z, gscale, lr, b1, b2, omb1, omb2, eps, wd, c1, c2);
+    adam_one(pi.w, gi.w, mi.w, vi.w, gscale, lr, b1, b2, omb1, omb2, eps, wd, c1, c2);
     m[i] = mi; v[i] = vi; p[i] = pi;
   }
 }
@@ -302,7 +324,13 @@ __global__ void __launch_bounds__(256) sgd4_kernel(float4* __restrict__ p, const
     p[i] = pi;
   }
 }
-__global__ void __launch_bounds__(256) sumsq4_kernel(const float4* __restrict__ g, size_t n4, float* out) {
+// Sum of squares in two stages: every workgroup leaves ONE partial in part[] (sumsq4_kernel over the aligned body, sumsq_kernel
+// over a misaligned call or the tail), sumsq_final_kernel adds the partials in double in a fixed order and adds the total to
+// *out once.  (Until round 15 every workgroup added its partial to *out with a float atomic: a chain of up to 1024 additions,
+// each rounded to the running total's ulp -- 5.9e-7 relative on 1 M elements where a float32 pairwise sum stays under 6e-8 --
+// and in an order that changed from run to run.)
+constexpr int SUMSQ_MAX_BLOCKS = 1024;                     // per stage-one kernel; part[] holds 2 * SUMSQ_MAX_BLOCKS floats
+__global__ void __launch_bounds__(256) sumsq4_kernel(const float4* __restrict__ g, size_t n4, float* __restrict__ part) {
   float s0 = 0.f, s1 = 0.f;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
     const float4 x = g[i];
@@ -312,18 +340,32 @@ __global__ void __launch_bounds__(256) sumsq4_kernel(const float4* __restrict__ 
   __shared__ float red[4];
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(out, (red[0] + red[1]) + (red[2] + red[3]));
+  if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-__global__ void sumsq_kernel(const float* g, size_t n, float* out) {
+__global__ void sumsq_kernel(const float* g, size_t n, float* __restrict__ part) {
   float s = 0.f;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
     s += g[i] * g[i];
   s = wave_sum(s);
-  __shared__ float part[4];
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+  __shared__ float red[4];
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(out, part[0] + part[1] + part[2] + part[3]);
+  if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// one workgroup: out += sum of part[0 .. nparts) (nparts <= 2 * SUMSQ_MAX_BLOCKS), in double, in a fixed order
+__global__ void __launch_bounds__(256) sumsq_final_kernel(const float* __restrict__ part, int nparts, float* out) {
+  double s = 0.0;
+  for (int i = threadIdx.x; i < nparts; i += 256) s += (double)part[i];
+  __shared__ double red[256];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) atomicAdd(out, (float)red[0]);     // (atomic: the word may collect several calls, as before)
 }
 
 }  // namespace mmnas
@@ -456,21 +498,20 @@ extern "C" int mmnas_adam_step(float* p, const float* g, float* m, float* v, siz
                                int step, void* stream) {
   if (n == 0) return MMNAS_OK;
   MMNAS_REQUIRE(p && g && m && v && step >= 1, MMNAS_E_ARG, "mmnas_adam_step: bad arguments");
-  const float c1 = 1.f - powf(beta1, (float)step);
-  const float c2 = sqrtf(1.f - powf(beta2, (float)step));
+  const AdamCoef k = adam_coef(beta1, beta2, step);
   // 16-byte path for the aligned body, the scalar kernel for a misaligned call or the tail (< 4 elements)
   const bool al16 = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
   const size_t n4 = al16 ? n / 4 : 0, done = 4 * n4;
   if (n4) {
     const int blocks4 = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
     MMNAS_LAUNCH(adam4_kernel, dim3(blocks4), dim3(256), 0, (hipStream_t)stream, (float4*)p, (const float4*)g, (float4*)m, (float4*)v, n4,
-                 lr, beta1, beta2, eps, weight_decay, sumsq, max_norm, c1, c2);
+                 lr, beta1, beta2, k.omb1, k.omb2, eps, weight_decay, sumsq, max_norm, k.c1, k.c2s);
   }
   if (done < n) {
     const size_t r = n - done;
     const int blocks = (int)((r + 255) / 256 < 4096 ? (r + 255) / 256 : 4096);
     MMNAS_LAUNCH(adam_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p + done, g + done, m + done, v + done, r, lr, beta1,
-                 beta2, eps, weight_decay, sumsq, max_norm, c1, c2);
+                 beta2, k.omb1, k.omb2, eps, weight_decay, sumsq, max_norm, k.c1, k.c2s);
   }
   return check_launch("adam_step");
 }
@@ -507,18 +548,39 @@ extern "C" int mmnas_sgd_step(float* p, const float* g, float* buf, size_t n, fl
   return check_launch("sgd_step");
 }
 
+// The partials' buffer of mmnas_sumsq: one per stream (calls on one stream are ordered, calls on two streams never share a
+// buffer), allocated at the stream's first call and kept for the life of the process.
+static float* sumsq_partials(hipStream_t st) {
+  static std::mutex mu;
+  static std::vector<std::pair<hipStream_t, float*>> table;
+  std::lock_guard<std::mutex> g(mu);
+  for (const auto& e : table)
+    if (e.first == st) return e.second;
+  float* p = nullptr;
+  if (hipMalloc(&p, (size_t)2 * SUMSQ_MAX_BLOCKS * sizeof(float)) != hipSuccess) return nullptr;
+  table.emplace_back(st, p);
+  return p;
+}
+
 extern "C" int mmnas_sumsq(const float* g, size_t n, float* out, void* stream) {
   if (n == 0) return MMNAS_OK;
   MMNAS_REQUIRE(g && out, MMNAS_E_ARG, "mmnas_sumsq: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  float* part = sumsq_partials(st);
+  MMNAS_REQUIRE(part, MMNAS_E_LAUNCH, "mmnas_sumsq: no memory for the partial sums");
   const size_t n4 = (((uintptr_t)g & 15) == 0) ? n / 4 : 0, done = 4 * n4;
+  int nparts = 0;
   if (n4) {
-    const int blocks4 = (int)((n4 + 255) / 256 < 1024 ? (n4 + 255) / 256 : 1024);
-    MMNAS_LAUNCH(sumsq4_kernel, dim3(blocks4), dim3(256), 0, (hipStream_t)stream, (const float4*)g, n4, out);
+    const int blocks4 = (int)((n4 + 255) / 256 < (size_t)SUMSQ_MAX_BLOCKS ? (n4 + 255) / 256 : SUMSQ_MAX_BLOCKS);
+    MMNAS_LAUNCH(sumsq4_kernel, dim3(blocks4), dim3(256), 0, st, (const float4*)g, n4, part);
+    nparts = blocks4;
   }
   if (done < n) {
     const size_t r = n - done;
-    const int blocks = (int)((r + 255) / 256 < 1024 ? (r + 255) / 256 : 1024);
-    MMNAS_LAUNCH(sumsq_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g + done, r, out);
+    const int blocks = (int)((r + 255) / 256 < (size_t)SUMSQ_MAX_BLOCKS ? (r + 255) / 256 : SUMSQ_MAX_BLOCKS);
+    MMNAS_LAUNCH(sumsq_kernel, dim3(blocks), dim3(256), 0, st, g + done, r, part + nparts);
+    nparts += blocks;
   }
+  MMNAS_LAUNCH(sumsq_final_kernel, dim3(1), dim3(256), 0, st, (const float*)part, nparts, out);
   return check_launch("sumsq");
 }
