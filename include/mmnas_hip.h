@@ -392,6 +392,43 @@ int mmnas_alpha_two_step_cost(float* prob, const float* gate_grad, float* m, flo
                               float* stats, int rows, int width, const int* pair_host, float lr, float beta1, float beta2,
                               float eps, float weight_decay, float cost_weight, float cost_ref, int cost_form, int step,
                               void* stream);
+/* The REINFORCE architecture update (ProxylessNAS section 3.3.2; MnasNet's reward): no gate gradient, no backward.  The caller
+ * ran M sampled architectures forward; choice_host is a HOST array [M, rows] of bytes, the candidate a_ir sample i took in row
+ * r, read at call time and carried in the kernel arguments as pair_host is (no device copy, no synchronisation), checked
+ * against the HOST array n_choices_host [rows] of live columns per row.  quality is a DEVICE float[M], the task reward Q_i of
+ * each sample, written by whatever computed it and never read by the host.  cost (nullable) [rows, width] prices the sample:
+ *   C_i = sum_r cost[r, a_ir]                                (cost == NULL or cost_weight == 0: R_i = Q_i)
+ *   reward_form 0 ('mul'): R_i = Q_i * (C_i / cost_ref)^cost_weight        (C_i <= 0: factor 1)
+ *   reward_form 1 ('add'): R_i = Q_i + cost_weight * log(C_i / cost_ref)   (C_i <= 0: term 0)
+ *   Rbar = mean_i R_i;  b = initialised ? baseline : Rbar;  A_i = R_i - b
+ *   g[r, j] = -(1 / M) (sum_{i: a_ir = j} A_i - p[r, j] sum_i A_i),  p = softmax(alpha_r) over the live columns, alphas BEFORE
+ *   the update: the gradient of -(1 / M) sum_i A_i sum_r log p[r, a_ir] with A held constant
+ *   Adam (torch's rule) on g + weight_decay * alpha; prob_grad (nullable, overwritten) keeps the undecayed g
+ *   baseline <- initialised ? decay * baseline + (1 - decay) * Rbar : Rbar;  initialised <- 1
+ * baseline is a DEVICE float[2] (value, initialised).  stats (nullable) is a DEVICE float[M + 3]: R_0 .. R_{M-1}, Rbar, the b this
+ * update used, the baseline after it.  err is a DEVICE int: if any Q_i or R_i is not finite it is set to 1 and NOTHING else is
+ * written (alphas, moments, prob_grad, baseline and stats stay); otherwise it is left as it is.
+ * With M = 1 the first update has b = R_0, A = 0: it moves the moments' decay and, with weight_decay, nothing else -- the rule,
+ * not a defect (a single sample says nothing against a baseline it defines).
+ * One launch of ONE 256-thread workgroup that walks the rows r, r + 256, ...  Thread i prices sample i, rows ascending: C_i and
+ * the cost factor / term are formed in double (cost_weight and cost_ref as the floats they are passed as) and R_i is rounded
+ * once to float.  Rbar, A_i,
+ * sum_i A_i and sum_{i: a_ir = j} A_i are formed in double from the float R_i, samples ascending, and g is rounded once.  (The
+ * first update has sum_i A_i = 0 up to rounding; in double that noise is 1e-17 and Adam's eps swallows it, and a column every
+ * sample chose receives -(1 - p) sum_i A_i / M exactly.  Float sums leave 1e-9 there, which Adam turns into a step.)  No
+ * atomics anywhere: the same inputs give the same bits.
+ * Limits (MMNAS_E_SHAPE): M <= 256, width <= 256, M * rows <= 3072 -- the indices share the 4 KB kernel argument block with the
+ * other arguments; 300 x 4 and 128 x 16 fit.  padding columns hold -inf in prob and stay 0 in m / v.
+ * beta1 / beta2 / baseline_decay are read as the decimals the caller wrote, 1 - beta and the bias corrections are formed in
+ * double on the host, as in the _cost entries.
+ * MMNAS_E_ARG, before any launch: a null pointer (prob_grad, cost and stats excepted), reward_form outside 0 / 1, cost_ref not
+ * finite or <= 0, cost_weight not finite (any sign is allowed), baseline_decay outside [0, 1), M < 1, step < 1, width < 1,
+ * rows < 0, a row with n_choices outside 1..width, an index outside its row's live columns. */
+int mmnas_alpha_reinforce_step(float* prob, float* m, float* v, float* prob_grad, int rows, int width,
+                               const unsigned char* choice_host, const int* n_choices_host, int M, const float* quality,
+                               const float* cost, float cost_weight, float cost_ref, int reward_form, float* baseline,
+                               float baseline_decay, float* stats, int* err, float lr, float beta1, float beta2, float eps,
+                               float weight_decay, int step, void* stream);
 
 /* nn.Embedding backward (hygr_vqa.py:85,105; aten embedding_dense_backward): dW[idx[t], :] += dy[t, :] for the n_tok
  * int64 token indices -- straight into the (already zeroed or accumulating) gradient buffer instead of a dense
@@ -909,6 +946,12 @@ int mmnas_vgd_ground(const float* pred_scores, const float* pred_reg, const floa
  *   mmnas_vqa_answer_targets: the loader's proc_ans / get_score (load_data_vqa.py:299-333) from answer indices: ans_ix [B, n]
  *     (-1 = not in the vocabulary; outside -1..A-1: flag 2, ignored), out [B, A] float32 = 0 / .3 / .6 / .9 / 1 by how often
  *     the column occurs in the row (every element written).  1 <= n <= 64.  One wave per row.
+ *   mmnas_vqa_soft_accuracy: the VQA soft score of the predicted answer under the loader's proc_ans targets, the quantity
+ *     train_vqa's training accuracy is a proxy for: per_row[b] (nullable [B]) = target[b, argmax_a logits[b, a]] (the argmax as
+ *     mmnas_vqa_answer's; rows ld_logits / ld_target >= A floats apart), out[0] = mean_b per_row[b].  ONE launch of one
+ *     256-thread workgroup: wave w takes the rows w, w + 4, ... in that order and sums them in double, the four sums meet as
+ *     (s0 + s1) + (s2 + s3) -- no atomics, the same bits on every call, nothing for the host to read before out is used.
+ *     A NaN logit stores 1 to *nan_flag (otherwise left as it is).  B >= 1.
  * Host-side: negative sizes, ld < A, a type count or n out of range and null pointers return MMNAS_E_SHAPE / _ARG.
  * ------------------------------------------------------------------------------------------ */
 int mmnas_vqa_answer(const float* logits, int B, int A, long ld, const int* slot_idx, long slot_base, int slot_step, int nslots,
@@ -917,6 +960,8 @@ int mmnas_vqa_answer(const float* logits, int B, int A, long ld, const int* slot
 int mmnas_vqa_accuracy(const int* credit, const int* qmap, const int* ans_type, const int* ques_type, int N, int nq, int n_at,
                        int n_qt, long long* totals, int* err_flag, void* stream);
 int mmnas_vqa_answer_targets(const int* ans_ix, int B, int n, int A, float* out, int* err_flag, void* stream);
+int mmnas_vqa_soft_accuracy(const float* logits, long ld_logits, const float* target, long ld_target, int B, int A, float* per_row,
+                            float* out, int* nan_flag, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Grounding and retrieval training losses (configs[3] / [4], train_vgd / train_itm; mmnas_amd/losses.py).  One launch forward

@@ -202,6 +202,8 @@ SYMBOLS = {
     'mmnas_alpha_two_step': (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, C.POINTER(C.c_int), _f, _f, _f, _f, _f, _i, _fp]),
     'mmnas_alpha_full_step_cost': (_i, [_fp] * 7 + [_i, _i, _f, _f, _f, _f, _f, _f, _f, _i, _i, _fp]),
     'mmnas_alpha_two_step_cost': (_i, [_fp] * 7 + [_i, _i, C.POINTER(C.c_int), _f, _f, _f, _f, _f, _f, _f, _i, _i, _fp]),
+    'mmnas_alpha_reinforce_step': (_i, [_fp] * 4 + [_i, _i, C.POINTER(C.c_ubyte), C.POINTER(C.c_int), _i, _fp, _fp, _f, _f, _i, _fp, _f,
+                                        _fp, _fp, _f, _f, _f, _f, _f, _i, _fp]),
     'mmnas_embedding_bwd': (_i, [_fp, _fp, _fp, C.c_long, _i, C.c_long, _fp]),
     'mmnas_node_mix_fwd': (_i, [_fp, _fp, _fp, _i, _fp, _fp, _i, _i, _f, _fp]),
     'mmnas_node_mix_bwd': (_i, [_fp, _fp, _fp, _i, _fp, _fp, _fp, _i, _fp, _fp, _i, _i, _f, _fp]),
@@ -236,6 +238,7 @@ SYMBOLS = {
     'mmnas_vqa_answer': (_i, [_fp, _i, _i, C.c_long, _fp, C.c_long, _i, _i] + [_fp] * 4 + [_i] + [_fp] * 5),
     'mmnas_vqa_accuracy': (_i, [_fp] * 4 + [_i] * 4 + [_fp, _fp, _fp]),
     'mmnas_vqa_answer_targets': (_i, [_fp, _i, _i, _i, _fp, _fp, _fp]),
+    'mmnas_vqa_soft_accuracy': (_i, [_fp, C.c_long, _fp, C.c_long, _i, _i, _fp, _fp, _fp, _fp]),
     'mmnas_vgd_loss_fwd': (_i, [_fp] * 6 + [_i] * 6 + [C.c_double, C.c_double] + [_fp] * 5),
     'mmnas_itm_triplet_loss_fwd': (_i, [_fp, _fp, _fp, C.c_long, _i, _f, _i, _fp, _fp, _fp]),
     'mmnas_loss_grad_scale': (_i, [_fp, _fp, _fp, _sz, _fp]),

@@ -13,6 +13,8 @@
   credits by answer and question type into VQAEval.accuracy; results() gives the result list the reference dumps.
 * answer_indices / answer_targets -- the loader's proc_ans soft targets (load_data_vqa.py:299-333): the answer strings become
   [B, n] vocabulary indices on the host, the dense [B, A] rows are written on the device.
+* soft_accuracy / SoftAccuracyReward -- the soft score of the predicted answer under those targets, target[b, argmax logits[b]],
+  and its batch mean as a device scalar (mmnas_vqa_soft_accuracy): the reward of a REINFORCE architecture step.
 
 The answer normalisers are arguments, not part of this package: with the reference checkout, pass
 mmnas.utils.answer_punct.process_punctuation / process_digit_article, which use the same tables as VQAEval.
@@ -28,7 +30,8 @@ import torch
 
 from . import _lib as L
 
-__all__ = ['AnswerCredit', 'VqaEvaluator', 'answer_batch', 'answer_indices', 'answer_targets', 'AnsweringError']
+__all__ = ['AnswerCredit', 'VqaEvaluator', 'answer_batch', 'answer_indices', 'answer_targets', 'AnsweringError', 'soft_accuracy',
+           'SoftAccuracyReward']
 
 MAX_TYPES = 256
 MAX_ANSWERS = 64       # annotator answers per question (n)
@@ -289,6 +292,49 @@ def answer_batch(logits, index=None, credit=None, check=True):
     if check:
         _raise_flag(int(flag.item()), 'answer_batch')
     return dict(pred=pred, credit=cr)
+
+
+def soft_accuracy(logits, target, per_row=False, check=True):
+    """The VQA soft score of the predicted answers: logits, target [B, A] float32 (row strides may exceed A), target the loader's
+    proc_ans rows.  score[b] = target[b, argmax_a logits[b, a]] (np.argmax's rule: the lowest index of the maximum, infinities
+    ordinary values); returns their mean over the batch as a 0-dim tensor on the device of logits, summed in float64 in a
+    fixed order -- one launch, nothing read back.  per_row=True returns (mean, score [B]).  A NaN logit raises AnsweringError;
+    check=False skips reading back the device's flag (a host sync): the call then never synchronises."""
+    logits, A, ld = _logits_rows(logits)
+    if not isinstance(target, torch.Tensor) or target.dtype != torch.float32 or tuple(target.shape) != tuple(logits.shape):
+        raise TypeError('soft_accuracy: target must be a float32 tensor of the logits\' shape %s' % (tuple(logits.shape),))
+    if target.device != logits.device:
+        raise ValueError('soft_accuracy: target is on %s, logits on %s' % (target.device, logits.device))
+    target, _, ldt = _logits_rows(target)
+    B = logits.shape[0]
+    if B < 1:
+        raise ValueError('soft_accuracy: an empty batch has no mean')
+    if not logits.is_cuda:
+        x = logits.detach().numpy()
+        if np.isnan(x).any():
+            raise AnsweringError('soft_accuracy: a NaN logit')
+        rows = target.detach().numpy()[np.arange(B), np.argmax(x, axis=1)]
+        mean = torch.tensor(np.float32(rows.astype(np.float64).sum() / B))
+        return (mean, torch.from_numpy(rows.copy())) if per_row else mean
+    dev = logits.device
+    out = torch.empty(1, dtype=torch.float32, device=dev)
+    rows = torch.empty(B, dtype=torch.float32, device=dev) if per_row else None
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().mmnas_vqa_soft_accuracy(logits.data_ptr(), ld, target.data_ptr(), ldt, B, A, L.ptr(rows), L.ptr(out),
+                                                L.ptr(flag), L.stream()))
+    if check:
+        _raise_flag(int(flag.item()), 'soft_accuracy')
+    return (out[0], rows) if per_row else out[0]
+
+
+class SoftAccuracyReward:
+    """reward(pred, target) of harness.SearchLoop(arch_mode='reinforce'): the batch's VQA soft accuracy as a device scalar,
+    never synchronising (a NaN logit gives a NaN-free but meaningless score here; the update's own `err` flag guards the
+    rewards it is fed)."""
+
+    def __call__(self, pred, target):
+        return soft_accuracy(pred, target, check=False)
 
 
 # ---- accuracy --------------------------------------------------------------------------------------------------------------------

@@ -4,7 +4,9 @@
 //   * mmnas_vqa_accuracy       -- the sums of VQAEval.setAccuracy (vqaEval.py:143-146) as exact integers, by answer type and
 //     by question type;
 //   * mmnas_vqa_answer_targets -- the loader's soft answer targets (load_data_vqa.py:299-333 proc_ans / get_score) for a batch
-//     of answer-index lists.
+//     of answer-index lists;
+//   * mmnas_vqa_soft_accuracy  -- those targets' score of the predicted answer, target[b, argmax logits[b]], and its batch
+//     mean as a device scalar: the reward of a REINFORCE architecture step (harness.SearchLoop(arch_mode='reinforce')).
 // The argmax and the targets run one wave per row, four rows per 256-thread workgroup.  Logit rows are 4-byte aligned only
 // (3129 floats), so every load is a single dword.
 #include "common.h"
@@ -163,6 +165,52 @@ __global__ void __launch_bounds__(256) vqa_answer_targets_kernel(const int* __re
   if (__ballot(bad) && lane == 0) atomicOr(err, VQA_ERR_INDEX);
 }
 
+// ------------------------------------------------------------------------------------------
+// soft accuracy: target[b, argmax_a logits[b, a]] per row and its mean.  ONE workgroup: wave w takes the rows w, w + 4, ... in
+// that order and adds their scores in double; the four sums meet in LDS as (s0 + s1) + (s2 + s3).  No atomics: the NaN flag is
+// a plain store of 1.
+// ------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) vqa_soft_accuracy_kernel(const float* __restrict__ logits, long ld, const float* __restrict__ target,
+                                                                long ldt, int B, int A, float* __restrict__ per_row,
+                                                                float* __restrict__ out, int* __restrict__ nan_flag) {
+  __shared__ double part[4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  double sum = 0.0;
+  bool nan = false;
+  for (int b = w; b < B; b += 4) {
+    const float* row = logits + (size_t)b * ld;
+    float bv = 0.f;
+    int bi = -1;
+#pragma unroll 4
+    for (int c = lane; c < A; c += 64) {
+      const float v = row[c];
+      if (vqa_before(v, c, bv, bi)) {
+        bv = v;
+        bi = c;
+      }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      const float ov = __shfl_xor(bv, off);
+      const int oi = __shfl_xor(bi, off);
+      if (oi >= 0 && vqa_before(ov, oi, bv, bi)) {
+        bv = ov;
+        bi = oi;
+      }
+    }
+    nan |= bv != bv;                       // NaN ranks first: the row holds one iff its maximum is NaN
+    const float s = target[(size_t)b * ldt + bi];   // (A >= 1: every wave ends with 0 <= bi < A)
+    if (per_row && lane == 0) per_row[b] = s;
+    sum += (double)s;
+  }
+  if (lane == 0) {
+    part[w] = sum;
+    if (nan) *nan_flag = 1;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) out[0] = (float)(((part[0] + part[1]) + (part[2] + part[3])) / (double)B);
+}
+
 }  // namespace mmnas
 
 using namespace mmnas;
@@ -199,4 +247,14 @@ extern "C" int mmnas_vqa_answer_targets(const int* ans_ix, int B, int n, int A, 
   if (B == 0) return MMNAS_OK;
   MMNAS_LAUNCH(vqa_answer_targets_kernel, dim3(cdiv(B, 4)), dim3(256), 0, (hipStream_t)stream, ans_ix, B, n, A, out, err_flag);
   return check_launch("vqa_answer_targets");
+}
+
+extern "C" int mmnas_vqa_soft_accuracy(const float* logits, long ld_logits, const float* target, long ld_target, int B, int A,
+                                       float* per_row, float* out, int* nan_flag, void* stream) {
+  MMNAS_REQUIRE(B >= 1 && A >= 1 && ld_logits >= A && ld_target >= A, MMNAS_E_SHAPE,
+                "vqa_soft_accuracy: B=%d A=%d ld %ld / %ld (B >= 1, 1 <= A <= ld)", B, A, ld_logits, ld_target);
+  MMNAS_REQUIRE(logits && target && out && nan_flag, MMNAS_E_ARG, "vqa_soft_accuracy: null pointer");
+  MMNAS_LAUNCH(vqa_soft_accuracy_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, ld_logits, target, ld_target, B, A, per_row,
+               out, nan_flag);
+  return check_launch("vqa_soft_accuracy");
 }

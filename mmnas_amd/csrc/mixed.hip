@@ -514,6 +514,117 @@ __global__ __launch_bounds__(256) void alpha_two_step_cost_kernel(float* __restr
                         pa.ij[2 * r + 1], ac.cost, k);
 }
 
+// The REINFORCE architecture update (ProxylessNAS section 3.3.2, MnasNet's reward): M sampled architectures a_i (one candidate
+// per row), their task rewards Q_i on the device, an optional price C_i = sum_r cost[r, a_ir] of each, a moving-average baseline.
+// The sampled indices travel in the kernel arguments, one byte each.
+constexpr int ALPHA_REINFORCE_MAX_CHOICES = 3072;          // M * rows: 3 KB of the 4 KB argument block (300 x 4, 128 x 16, ...)
+constexpr int ALPHA_REINFORCE_MAX_SAMPLES = 256;           // M: thread i prices sample i
+struct AlphaChoiceArgs { unsigned char a[ALPHA_REINFORCE_MAX_CHOICES]; };   // [M, rows]
+
+struct AlphaReinforce {
+  const float* quality;  // [M]
+  const float* cost;     // nullable (also when cost_weight == 0): R_i = Q_i
+  float* baseline;       // (value, initialised)
+  float* stats;          // nullable: R_0 .. R_{M-1}, mean R, baseline used, baseline after
+  int* err;
+  double decay, omd;     // baseline_decay and 1 - baseline_decay, formed on the host from the decimal the caller wrote
+  float weight, ref;
+  int form;              // 0 mul, 1 add
+  int M;
+};
+
+// one row of the REINFORCE gradient + Adam.  sA: A_i = R_i - b in LDS, in double; sum_a their sum, samples ascending.  The sum
+// over the samples that chose a column runs in double in the same order: where every sample chose one column it IS sum_a, bit
+// for bit, and the column's gradient -(1 - p) sum_a / M is as small as sum_a is (the first update: rounding noise of 1e-17,
+// which Adam's eps = 1e-8 still swallows; float sums would leave 1e-9 there and Adam would step by it).  The row arithmetic (softmax over the
+// live columns, the Adam body) is alpha_full_row's text; it is written out again here and not shared through a helper, so that
+// the four existing alpha kernels keep their instruction streams, registers and bits exactly.
+__device__ __forceinline__ void alpha_reinforce_row(float* __restrict__ prob, float* __restrict__ m, float* __restrict__ v,
+                                                    float* __restrict__ prob_grad, int r, int rows, int width, int M,
+                                                    const double* sA, double sum_a, const AlphaChoiceArgs& ch, float lr, float b1,
+                                                    float b2, float omb1, float omb2, float eps, float c1, float c2s, float wd) {
+  float* a = prob + (size_t)r * width;
+  float mx = -INFINITY;
+  for (int i = 0; i < width; ++i) mx = fmaxf(mx, a[i]);
+  float den = 0.f;
+  for (int i = 0; i < width; ++i) den += expf(a[i] - mx);   // padding columns hold -inf: exp = 0
+  for (int i = 0; i < width; ++i) {
+    const float ai = a[i];
+    const float p = expf(ai - mx) / den;
+    double hit = 0.0;                                       // sum of A_k over the samples that chose column i, k ascending
+    for (int k = 0; k < M; ++k)
+      if ((int)ch.a[k * rows + r] == i) hit += sA[k];
+    float grad = (float)(-(hit - (double)p * sum_a) / (double)M);
+    const size_t o = (size_t)r * width + i;
+    if (prob_grad) prob_grad[o] = grad;
+    if (!(ai > -INFINITY)) continue;                        // padding column: stays -inf, its moments untouched
+    if (wd != 0.f) grad += wd * ai;                         // torch Adam's weight_decay: prob_grad keeps the undecayed gradient
+    const float mi = b1 * m[o] + omb1 * grad;
+    const float vi = b2 * v[o] + omb2 * grad * grad;
+    m[o] = mi; v[o] = vi;
+    a[i] = ai - (lr / c1) * mi / (sqrtf(vi) / c2s + eps);
+  }
+}
+
+// ONE workgroup of 256 threads.  Thread i < M prices sample i (rows ascending, in double) and forms R_i; a non-finite Q_i or R_i ends the
+// kernel with *err = 1 before anything is written.  Every thread then forms mean R, b and sum_i A_i in double, samples
+// ascending (no atomics, no cross-lane sums: the same bits on every call), thread 0 moves the baseline, and the threads walk
+// the rows r, r + 256, ...  The baseline is read by everyone before the barrier and written by thread 0 after it.
+__global__ __launch_bounds__(256) void alpha_reinforce_step_kernel(float* __restrict__ prob, float* __restrict__ m,
+                                                                   float* __restrict__ v, float* __restrict__ prob_grad, int rows,
+                                                                   int width, float lr, float b1, float b2, float omb1, float omb2,
+                                                                   float eps, float c1, float c2s, float wd, AlphaReinforce ar,
+                                                                   AlphaChoiceArgs ch) {
+  __shared__ float sR[ALPHA_REINFORCE_MAX_SAMPLES];
+  __shared__ double sA[ALPHA_REINFORCE_MAX_SAMPLES];
+  __shared__ int bad;
+  const int t = threadIdx.x, M = ar.M;
+  if (t == 0) bad = 0;
+  __syncthreads();
+  if (t < M) {
+    const float q = ar.quality[t];
+    float R = q;
+    if (ar.cost) {
+      double C = 0.0;                                       // the price and the reward in double, R_i rounded once: A_i = R_i - b
+      for (int r = 0; r < rows; ++r) C += (double)ar.cost[(size_t)r * width + ch.a[t * rows + r]];      // cancels, and M values cost nothing
+      if (C > 0.0) {
+        const double ratio = C / (double)ar.ref, w = (double)ar.weight;
+        R = (float)(ar.form == 0 ? (double)q * pow(ratio, w) : (double)q + w * log(ratio));
+      }
+    }
+    sR[t] = R;
+    if (!(fabsf(q) < INFINITY) || !(fabsf(R) < INFINITY)) bad = 1;      // (every writer stores the same value)
+  }
+  __syncthreads();
+  if (bad) {
+    if (t == 0) *ar.err = 1;
+    return;
+  }
+  double sum_r = 0.0;
+  for (int i = 0; i < M; ++i) sum_r += (double)sR[i];
+  const double rbar = sum_r / (double)M;
+  const float b_old = ar.baseline[0];
+  const bool init = ar.baseline[1] != 0.f;
+  const double b = init ? (double)b_old : rbar;
+  double sum_a = 0.0;
+  for (int i = 0; i < M; ++i) sum_a += (double)sR[i] - b;
+  if (t < M) sA[t] = (double)sR[t] - b;
+  __syncthreads();
+  if (t == 0) {
+    const float b_new = init ? (float)(ar.decay * (double)b_old + ar.omd * rbar) : (float)rbar;
+    ar.baseline[0] = b_new;
+    ar.baseline[1] = 1.f;
+    if (ar.stats) {
+      for (int i = 0; i < M; ++i) ar.stats[i] = sR[i];
+      ar.stats[M] = (float)rbar;
+      ar.stats[M + 1] = (float)b;
+      ar.stats[M + 2] = b_new;
+    }
+  }
+  for (int r = t; r < rows; r += 256)
+    alpha_reinforce_row(prob, m, v, prob_grad, r, rows, width, M, sA, sum_a, ch, lr, b1, b2, omb1, omb2, eps, c1, c2s, wd);
+}
+
 }  // namespace mmnas
 
 using namespace mmnas;
@@ -645,6 +756,47 @@ extern "C" int mmnas_alpha_two_step_cost(float* prob, const float* gate_grad, fl
   MMNAS_LAUNCH(alpha_two_step_cost_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, prob, gate_grad, m, v, prob_grad, rows, width,
                lr, beta1, beta2, k.omb1, k.omb2, eps, k.c1, k.c2s, weight_decay, pa, ac);
   return check_launch("alpha_two_step_cost");
+}
+
+extern "C" int mmnas_alpha_reinforce_step(float* prob, float* m, float* v, float* prob_grad, int rows, int width,
+                                          const unsigned char* choice_host, const int* n_choices_host, int M, const float* quality,
+                                          const float* cost, float cost_weight, float cost_ref, int reward_form, float* baseline,
+                                          float baseline_decay, float* stats, int* err, float lr, float beta1, float beta2,
+                                          float eps, float weight_decay, int step, void* stream) {
+  const char* who = "mmnas_alpha_reinforce_step";
+  MMNAS_REQUIRE(rows >= 0 && M >= 1 && step >= 1 && width >= 1, MMNAS_E_ARG, "%s: rows=%d (>= 0) M=%d (>= 1) step=%d (>= 1) width=%d (>= 1)",
+                who, rows, M, step, width);
+  MMNAS_REQUIRE(reward_form == 0 || reward_form == 1, MMNAS_E_ARG, "%s: reward_form=%d (0 mul, 1 add)", who, reward_form);
+  MMNAS_REQUIRE(std::isfinite(cost_ref) && cost_ref > 0.f, MMNAS_E_ARG, "%s: cost_ref=%g must be finite and positive", who, (double)cost_ref);
+  MMNAS_REQUIRE(std::isfinite(cost_weight), MMNAS_E_ARG, "%s: cost_weight=%g must be finite", who, (double)cost_weight);
+  MMNAS_REQUIRE(baseline_decay >= 0.f && baseline_decay < 1.f, MMNAS_E_ARG, "%s: baseline_decay=%g outside [0, 1)", who, (double)baseline_decay);
+  MMNAS_REQUIRE(prob && m && v && choice_host && n_choices_host && quality && baseline && err, MMNAS_E_ARG, "%s: null pointer", who);
+  MMNAS_REQUIRE(M <= ALPHA_REINFORCE_MAX_SAMPLES && width <= 256 && (long)M * rows <= ALPHA_REINFORCE_MAX_CHOICES, MMNAS_E_SHAPE,
+                "%s: M=%d (<= %d) width=%d (<= 256) M * rows=%ld (<= %d: the indices travel in the kernel arguments)", who, M,
+                ALPHA_REINFORCE_MAX_SAMPLES, width, (long)M * rows, ALPHA_REINFORCE_MAX_CHOICES);
+  for (int r = 0; r < rows; ++r)
+    MMNAS_REQUIRE(n_choices_host[r] >= 1 && n_choices_host[r] <= width, MMNAS_E_ARG, "%s: row %d has %d live columns of %d", who, r,
+                  n_choices_host[r], width);
+  AlphaChoiceArgs ch;
+  memset(&ch, 0, sizeof(ch));
+  for (int i = 0; i < M; ++i)
+    for (int r = 0; r < rows; ++r) {
+      const int a = choice_host[(size_t)i * rows + r];
+      MMNAS_REQUIRE(a < n_choices_host[r], MMNAS_E_ARG, "%s: sample %d, row %d: candidate %d outside 0..%d", who, i, r, a,
+                    n_choices_host[r] - 1);
+      ch.a[i * rows + r] = (unsigned char)a;
+    }
+  const AdamCoef k = adam_coef(beta1, beta2, step);
+  const double decay = decimal_of(baseline_decay);
+  AlphaReinforce ar;
+  ar.quality = quality;
+  ar.cost = cost_weight != 0.f ? cost : nullptr;
+  ar.baseline = baseline; ar.stats = stats; ar.err = err;
+  ar.decay = decay; ar.omd = 1.0 - decay;
+  ar.weight = cost_weight; ar.ref = cost_ref; ar.form = reward_form; ar.M = M;
+  MMNAS_LAUNCH(alpha_reinforce_step_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, prob, m, v, prob_grad, rows, width, lr, beta1,
+               beta2, k.omb1, k.omb2, eps, k.c1, k.c2s, weight_decay, ar, ch);
+  return check_launch("alpha_reinforce_step");
 }
 
 

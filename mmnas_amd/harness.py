@@ -152,6 +152,66 @@ def hard_negative_indices(scores, neg_idx, hard_size):
     return neg_idx.to(scores.device)[rows, top]
 
 
+class NegLossReward:
+    """reward(pred, target) = -scale * loss_fn(pred, target): the default reward of SearchLoop(arch_mode='reinforce'), the
+    loop's own loss with scale = 1 / batch size.  Works with every loss of the three tasks (VgdLoss and BatchedTriplet
+    included).  It is negative, so it suits reward_form 'add'; with 'mul' and a cost table the loop raises ValueError."""
+
+    def __init__(self, loss_fn, scale=1.0):
+        self.loss_fn, self.scale = loss_fn, float(scale)
+
+    def __call__(self, pred, target):
+        return -self.scale * self.loss_fn(pred, target)
+
+
+def _sample_plain(net, plan):
+    """One MODE = None sample that leaves every .grad as it is: drawn from the alphas, or an injected (active, inactive)
+    list per node."""
+    if plan is not None:
+        net.set_sampled(plan)
+        return
+    keep = getattr(net, 'keep_candidate_grads', False)
+    net.keep_candidate_grads = True
+    try:
+        net.reset_binary_gates()
+    finally:
+        net.keep_candidate_grads = keep
+
+
+def reinforce_arch_step(net, alpha_optim, reward, inputs, target, reducer=None, optimize=True, plan=None):
+    """The REINFORCE architecture step of SearchLoop(arch_mode='reinforce'): for each of alpha_optim.n_samples samples, sample
+    with MixedOp.MODE = None, record the row of active indices, run pred = net(inputs) in eval mode under no_grad and copy
+    reward(pred, target) (a device scalar) into alpha_optim.quality on the device; then alpha_optim.step(), one launch.  No
+    backward, no begin_arch_step, no write to a gradient or a weight; every module's training flag and MixedOp.MODE = None are
+    put back, also after an exception.  `plan`: a list of n_samples plans (tests, replay).  With a `reducer` whose process
+    group is up, the [M] rewards are averaged over the ranks with ONE all-reduce before the update: every rank samples the
+    same M architectures (mixed.seed_arch_sampler alike) on its own shard, so the ranks' alphas stay bit-identical.
+    Returns the mean quality, a device tensor."""
+    M = alpha_optim.n_samples
+    if plan is not None and len(plan) != M:
+        raise ValueError("arch_step(arch_mode='reinforce'): plan is a list of %d plans, one per sample, got %d" % (M, len(plan)))
+    flags = [(m, m.training) for m in net.modules()]
+    MixedOp.MODE = None
+    try:
+        net.eval()
+        with torch.no_grad():
+            for i in range(M):
+                _sample_plain(net, None if plan is None else plan[i])
+                alpha_optim.choice[i] = torch.tensor([int(m.active_index[0]) for m in net.redundant_modules])
+                q = reward(net(inputs), target)
+                alpha_optim.quality[i].copy_(q.detach().reshape(()))      # device to device
+    finally:
+        for m, t in flags:
+            m.training = t
+        MixedOp.MODE = None
+    if reducer is not None and reducer.comm:
+        dp._all_reduce_avg(alpha_optim.quality, reducer.group, reducer.world)
+    mean = alpha_optim.quality.mean()
+    if optimize:
+        alpha_optim.step()
+    return mean
+
+
 class ArchAdam:
     """alpha_optim of search_vqa.py:194 (torch.optim.Adam over alpha_prob_parameters, lr 0.1, betas (0, 0.999)) fused
     with Net_Search.set_arch_param_grad() for ALPHA_BINARY_MODE 'full': one kernel over the [n_nodes, width] blocks.
@@ -160,13 +220,24 @@ class ArchAdam:
     read from the nodes' active_index / inactive_index when step() runs.  The checkpoint format is the same in both modes.
     cost (a [nodes, width] block or a cost.CostTable) with cost_weight > 0: the expected-cost regulariser of a hardware-aware
     search, 'linear' or 'log' around cost_ref (default: the expected cost under uniform alphas), joins the objective in the
-    same launch (ops.alpha_cost_step); `cost_stats` then holds E_r per node, E and R of the last update on the device."""
+    same launch (ops.alpha_cost_step); `cost_stats` then holds E_r per node, E and R of the last update on the device.
+    mode='reinforce': the REINFORCE update (ops.alpha_reinforce_step) -- no gate gradients.  The caller records the
+    n_samples sampled architectures in `choice` (a CPU [M, nodes] int64 block) and their rewards in `quality` (device [M],
+    never read by the host); step() is the one launch.  `baseline` (device: value, initialised) is the moving average of the
+    mean reward, `reinforce_stats` (device [M + 3]) R_i, mean R, the baseline used and the one after, `err` (device int32)
+    is set -- and nothing moves -- when a reward is not finite.  Here cost prices the architecture actually sampled,
+    reward_form 'mul' (R = Q (C / cost_ref)^w) or 'add' (R = Q + w log(C / cost_ref)), and cost_weight may be negative.
+    state_dict() adds one top-level key 'reinforce' (baseline, initialised) to torch Adam's format."""
 
     def __init__(self, net, lr=0.1, betas=(0.0, 0.999), eps=1e-8, weight_decay=0, mode='full', cost=None, cost_weight=0.0,
-                 cost_form='linear', cost_ref=None):
-        if mode not in ('full', 'two'):
-            raise ValueError("ArchAdam: mode is 'full' or 'two', got %r" % (mode,))
+                 cost_form='linear', cost_ref=None, n_samples=4, baseline_decay=0.95, reward_form='mul'):
+        if mode not in ('full', 'two', 'reinforce'):
+            raise ValueError("ArchAdam: mode is 'full', 'two' or 'reinforce', got %r" % (mode,))
         self.mode = mode
+        if mode == 'reinforce':
+            self._init_reinforce(net, lr, betas, eps, weight_decay, cost, cost_weight, cost_ref, n_samples, baseline_decay,
+                                 reward_form)
+            return
         self.net, self.lr, self.betas, self.eps = net, lr, betas, eps
         self.weight_decay = weight_decay      # ALPHA_WEIGHT_DECAY (search_vqa.py:156-157,195)
         prob, _ = net._flat_alphas()
@@ -197,6 +268,63 @@ class ArchAdam:
             self.cost = block.to(prob.device).contiguous()
             self.cost_stats = torch.zeros(prob.shape[0] + 2, device=prob.device)      # E_r per node, E, R of the last update
 
+    def _init_reinforce(self, net, lr, betas, eps, weight_decay, cost, cost_weight, cost_ref, n_samples, baseline_decay, reward_form):
+        self.net, self.lr, self.betas, self.eps, self.weight_decay = net, lr, betas, eps, weight_decay
+        prob, _ = net._flat_alphas()
+        rows, width = prob.shape
+        self.m, self.v, self.steps = torch.zeros_like(prob), torch.zeros_like(prob), 0
+        if int(n_samples) != n_samples or n_samples < 1:
+            raise ValueError("ArchAdam(mode='reinforce'): n_samples >= 1, got %r" % (n_samples,))
+        self.n_samples = M = int(n_samples)
+        if prob.is_cuda and (M > ops.ALPHA_REINFORCE_MAX_SAMPLES or M * rows > ops.ALPHA_REINFORCE_MAX_CHOICES):
+            raise ValueError("ArchAdam(mode='reinforce'): %d samples of %d nodes; at most %d samples and %d indices travel with "
+                             "the launch" % (M, rows, ops.ALPHA_REINFORCE_MAX_SAMPLES, ops.ALPHA_REINFORCE_MAX_CHOICES))
+        if reward_form not in ops.REWARD_FORMS:
+            raise ValueError("ArchAdam: reward_form is 'mul' or 'add', got %r" % (reward_form,))
+        self.baseline_decay, self.reward_form = float(baseline_decay), reward_form
+        if not 0.0 <= self.baseline_decay < 1.0:
+            raise ValueError('ArchAdam: baseline_decay lies in [0, 1), got %r' % (baseline_decay,))
+        self.n_choices = [m.n_choices for m in net.redundant_modules]
+        self.cost = self.cost_stats = None
+        self.cost_weight, self.cost_form, self.cost_ref = float(cost_weight), None, cost_ref
+        if not math.isfinite(self.cost_weight):
+            raise ValueError('ArchAdam: cost_weight must be finite, got %r' % (cost_weight,))
+        if cost is not None and self.cost_weight != 0.0:
+            block = cost.for_net(net, 'linear') if isinstance(cost, cost_tables.CostTable) else cost
+            if tuple(block.shape) != (rows, width):
+                raise ValueError('ArchAdam: the cost block is %s, the alpha block %s' % (tuple(block.shape), (rows, width)))
+            block = cost_tables.check_block(block.detach().to('cpu', torch.float32), self.n_choices, 'linear')
+            if cost_ref is None:
+                self.cost_ref = cost_tables.uniform_expected(block, self.n_choices)
+            self.cost_ref = float(self.cost_ref)
+            if not (math.isfinite(self.cost_ref) and self.cost_ref > 0):
+                raise ValueError('ArchAdam: cost_ref must be finite and positive, got %r (the default is the expected cost under '
+                                 'uniform alphas: pass one for a table of zeros)' % (self.cost_ref,))
+            self.cost = block.to(prob.device).contiguous()
+        else:
+            self.cost_ref = 1.0 if cost_ref is None else float(cost_ref)
+        dev = prob.device
+        self.choice = torch.zeros(M, rows, dtype=torch.int64)                  # host: it travels in the kernel arguments
+        self.quality = torch.zeros(M, device=dev)
+        self.baseline = torch.zeros(2, device=dev)                             # (value, initialised)
+        self.reinforce_stats = torch.zeros(M + 3, device=dev)
+        self.err = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def _step_reinforce(self):
+        net = self.net
+        prob, _ = net._flat_alphas()
+        if net._flat_grads is None:
+            net._flat_grads = (torch.zeros_like(prob), torch.zeros_like(prob))
+        pg = net._flat_grads[1]
+        self.steps += 1
+        ops.alpha_reinforce_step(prob, self.m, self.v, pg, self.choice, self.quality, self.baseline, self.lr, self.betas, self.eps,
+                                 self.steps, self.weight_decay, cost=self.cost, cost_weight=self.cost_weight, cost_ref=self.cost_ref,
+                                 reward_form=self.reward_form, baseline_decay=self.baseline_decay, stats=self.reinforce_stats,
+                                 err=self.err, n_choices=self.n_choices)
+        for i, m in enumerate(net.redundant_modules):
+            m.alpha_prob.grad = pg[i, :m.n_choices]
+            m.alpha_version += 1                          # (the update wrote through the flat block: drop the sampling cache)
+
     def _sampled_pairs(self):
         pairs = []
         for i, m in enumerate(self.net.redundant_modules):
@@ -212,6 +340,8 @@ class ArchAdam:
         return pairs
 
     def step(self):
+        if self.mode == 'reinforce':
+            return self._step_reinforce()
         net = self.net
         prob, _ = net._flat_alphas()
         gg, pg = net._flat_grads
@@ -246,7 +376,11 @@ class ArchAdam:
         group = {'lr': self.lr, 'betas': tuple(self.betas), 'eps': self.eps, 'weight_decay': self.weight_decay, 'amsgrad': False,
                  'maximize': False, 'foreach': None, 'capturable': False, 'differentiable': False, 'fused': None,
                  'params': list(range(len(mods)))}
-        return {'state': state, 'param_groups': [group]}
+        sd = {'state': state, 'param_groups': [group]}
+        if self.mode == 'reinforce':      # (one host read: a checkpoint is being written anyway)
+            b = self.baseline.detach().cpu()
+            sd['reinforce'] = {'baseline': b[0].clone(), 'initialised': bool(b[1] != 0)}
+        return sd
 
     @torch.no_grad()
     def load_state_dict(self, sd):
@@ -271,6 +405,12 @@ class ArchAdam:
         if len(steps) > 1:
             raise ValueError('ArchAdam keeps one step count for all alpha blocks; the file holds %s' % sorted(steps))
         self.steps = steps.pop() if steps else 0
+        if self.mode == 'reinforce':      # (a file of another mode carries no baseline: a fresh one)
+            rf = sd.get('reinforce')
+            self.baseline.zero_()
+            if rf is not None and rf['initialised']:
+                self.baseline[0] = torch.as_tensor(rf['baseline'], dtype=torch.float32)
+                self.baseline[1] = 1.0
 
 
 class TrainLoop:
@@ -319,15 +459,28 @@ class SearchLoop:
     fused_arch_update (arch_mode='two' only): the architecture update as ArchAdam(mode='two') instead of the per-node
     statements around torch Adam; the checkpoints of the two are interchangeable.
     cost_table / cost_weight / cost_form / cost_ref: ArchAdam's expected-cost term ('two' carries it only under
-    fused_arch_update=True); without a table or with cost_weight 0 the architecture update is unchanged."""
+    fused_arch_update=True); without a table or with cost_weight 0 the architecture update is unchanged.
+    arch_mode='reinforce': the architecture step is `reinforce_samples` plain MODE = None forwards in eval mode under no_grad
+    -- no backward, no inactive candidates -- each scored by `reward(pred, target)` (a device scalar; default
+    NegLossReward(loss_fn, 1 / batch size)), then ArchAdam(mode='reinforce').step(), one launch.  cost_table / cost_weight /
+    cost_ref price the sampled architecture in `reward_form` 'mul' or 'add' (cost_weight may be negative: -0.07 is MnasNet's);
+    cost_form is not used.  With a process group the [M] rewards are averaged with one all-reduce before the update."""
 
     def __init__(self, net, loss_fn=None, net_lr=4e-4, net_betas=(0.9, 0.98), net_eps=1e-9, clip=1.0, epoch_steps=1000,
                  warmup=True, alpha_lr=0.1, alpha_betas=(0.0, 0.999), alpha_every=5, arch_mode='full', group=None,
                  absent_grads='zero', n_buckets=3, force_collectives=False, net_optim='wadam', net_momentum=0.9,
                  net_weight_decay=0.0, net_lr_min=0.0005, max_epoch=None, start_epoch=0, alpha_weight_decay=0.0,
-                 fused_arch_update=False, cost_table=None, cost_weight=0.0, cost_form='linear', cost_ref=None):
-        if arch_mode not in ('full', 'two'):
+                 fused_arch_update=False, cost_table=None, cost_weight=0.0, cost_form='linear', cost_ref=None,
+                 reinforce_samples=4, reward=None, baseline_decay=0.95, reward_form='mul'):
+        if arch_mode not in ('full', 'two', 'reinforce'):
             raise ValueError("ALPHA_BINARY_MODE is 'full' or 'two' (search_vqa.py:151), got %r" % (arch_mode,))
+        if arch_mode == 'reinforce':
+            if int(reinforce_samples) != reinforce_samples or reinforce_samples < 1:
+                raise ValueError("arch_mode='reinforce': reinforce_samples >= 1, got %r" % (reinforce_samples,))
+            priced = cost_table is not None and float(cost_weight) != 0.0
+            if priced and reward_form == 'mul' and (reward is None or isinstance(reward, NegLossReward)):
+                raise ValueError("arch_mode='reinforce': NegLossReward is negative, and a negative quality times the cost factor of "
+                                 "reward_form='mul' rewards cost: use reward_form='add' or a non-negative reward")
         if cost_table is not None and arch_mode == 'two' and not fused_arch_update:
             raise ValueError("cost_table with arch_mode='two' needs fused_arch_update=True: the per-node statements around torch "
                              "Adam do not carry the expected-cost term")
@@ -366,7 +519,12 @@ class SearchLoop:
         # (ops.alpha_two_step) for those three statements; with 'full' the keyword changes nothing
         self.fused_arch_update = bool(fused_arch_update) and arch_mode == 'two'
         cost_kw = dict(cost=cost_table, cost_weight=cost_weight, cost_form=cost_form, cost_ref=cost_ref)
-        if arch_mode == 'full':
+        self.reward = reward
+        if arch_mode == 'reinforce':
+            self.alpha_optim = ArchAdam(net, alpha_lr, alpha_betas, weight_decay=alpha_weight_decay, mode='reinforce',
+                                        cost=cost_table, cost_weight=cost_weight, cost_ref=cost_ref,
+                                        n_samples=int(reinforce_samples), baseline_decay=baseline_decay, reward_form=reward_form)
+        elif arch_mode == 'full':
             self.alpha_optim = ArchAdam(net, alpha_lr, alpha_betas, weight_decay=alpha_weight_decay, **cost_kw)
         elif self.fused_arch_update:
             self.alpha_optim = ArchAdam(net, alpha_lr, alpha_betas, weight_decay=alpha_weight_decay, mode='two', **cost_kw)
@@ -420,7 +578,16 @@ class SearchLoop:
         self.steps += 1
         return loss
 
+    def _reinforce_arch_step(self, inputs, target, optimize, plan):
+        reward = self.reward
+        if reward is None:      # the loop's own loss per sample of the batch, negated
+            reward = NegLossReward(self.loss_fn, 1.0 / max(int(target.shape[0]), 1))
+        return reinforce_arch_step(self.net, self.alpha_optim, reward, inputs, target, reducer=self.reducer, optimize=optimize,
+                                   plan=plan)
+
     def arch_step(self, inputs, target, optimize=True, plan=None):
+        if self.arch_mode == 'reinforce':
+            return self._reinforce_arch_step(inputs, target, optimize, plan)
         net, red = self.net, self.reducer
         MixedOp.MODE = self.arch_mode
         try:
