@@ -254,19 +254,24 @@ class ArchAdam:
                 raise ValueError("ArchAdam: cost_form is 'linear' or 'log', got %r" % (cost_form,))
             if not (math.isfinite(self.cost_weight) and self.cost_weight > 0):
                 raise ValueError('ArchAdam: cost_weight must be finite and not negative, got %r' % (cost_weight,))
-            n_choices = [m.n_choices for m in net.redundant_modules]
-            block = cost.for_net(net, cost_form) if isinstance(cost, cost_tables.CostTable) else cost
-            if tuple(block.shape) != tuple(prob.shape):
-                raise ValueError('ArchAdam: the cost block is %s, the alpha block %s' % (tuple(block.shape), tuple(prob.shape)))
-            block = cost_tables.check_block(block.detach().to('cpu', torch.float32), n_choices, cost_form)
-            if cost_ref is None:
-                self.cost_ref = cost_tables.uniform_expected(block, n_choices)
-            self.cost_ref = float(self.cost_ref)
-            if not (math.isfinite(self.cost_ref) and self.cost_ref > 0):
-                raise ValueError('ArchAdam: cost_ref must be finite and positive, got %r (the default is the expected cost under '
-                                 'uniform alphas: pass one for a table of zeros)' % (self.cost_ref,))
-            self.cost = block.to(prob.device).contiguous()
+            self.cost, self.cost_ref = self._prepare_cost(net, cost, cost_form, cost_ref)
             self.cost_stats = torch.zeros(prob.shape[0] + 2, device=prob.device)      # E_r per node, E, R of the last update
+
+    @staticmethod
+    def _prepare_cost(net, cost, form, cost_ref):
+        """-> (the checked [nodes, width] cost block on the alphas' device, cost_ref: by default the expected cost under
+        uniform alphas)."""
+        prob, _ = net._flat_alphas()
+        n_choices = [m.n_choices for m in net.redundant_modules]
+        block = cost.for_net(net, form) if isinstance(cost, cost_tables.CostTable) else cost
+        if tuple(block.shape) != tuple(prob.shape):
+            raise ValueError('ArchAdam: the cost block is %s, the alpha block %s' % (tuple(block.shape), tuple(prob.shape)))
+        block = cost_tables.check_block(block.detach().to('cpu', torch.float32), n_choices, form)
+        cost_ref = float(cost_tables.uniform_expected(block, n_choices) if cost_ref is None else cost_ref)
+        if not (math.isfinite(cost_ref) and cost_ref > 0):
+            raise ValueError('ArchAdam: cost_ref must be finite and positive, got %r (the default is the expected cost under '
+                             'uniform alphas: pass one for a table of zeros)' % (cost_ref,))
+        return block.to(prob.device).contiguous(), cost_ref
 
     def _init_reinforce(self, net, lr, betas, eps, weight_decay, cost, cost_weight, cost_ref, n_samples, baseline_decay, reward_form):
         self.net, self.lr, self.betas, self.eps, self.weight_decay = net, lr, betas, eps, weight_decay
@@ -290,17 +295,7 @@ class ArchAdam:
         if not math.isfinite(self.cost_weight):
             raise ValueError('ArchAdam: cost_weight must be finite, got %r' % (cost_weight,))
         if cost is not None and self.cost_weight != 0.0:
-            block = cost.for_net(net, 'linear') if isinstance(cost, cost_tables.CostTable) else cost
-            if tuple(block.shape) != (rows, width):
-                raise ValueError('ArchAdam: the cost block is %s, the alpha block %s' % (tuple(block.shape), (rows, width)))
-            block = cost_tables.check_block(block.detach().to('cpu', torch.float32), self.n_choices, 'linear')
-            if cost_ref is None:
-                self.cost_ref = cost_tables.uniform_expected(block, self.n_choices)
-            self.cost_ref = float(self.cost_ref)
-            if not (math.isfinite(self.cost_ref) and self.cost_ref > 0):
-                raise ValueError('ArchAdam: cost_ref must be finite and positive, got %r (the default is the expected cost under '
-                                 'uniform alphas: pass one for a table of zeros)' % (self.cost_ref,))
-            self.cost = block.to(prob.device).contiguous()
+            self.cost, self.cost_ref = self._prepare_cost(net, cost, 'linear', cost_ref)
         else:
             self.cost_ref = 1.0 if cost_ref is None else float(cost_ref)
         dev = prob.device
@@ -321,9 +316,7 @@ class ArchAdam:
                                  self.steps, self.weight_decay, cost=self.cost, cost_weight=self.cost_weight, cost_ref=self.cost_ref,
                                  reward_form=self.reward_form, baseline_decay=self.baseline_decay, stats=self.reinforce_stats,
                                  err=self.err, n_choices=self.n_choices)
-        for i, m in enumerate(net.redundant_modules):
-            m.alpha_prob.grad = pg[i, :m.n_choices]
-            m.alpha_version += 1                          # (the update wrote through the flat block: drop the sampling cache)
+        self._publish(pg)
 
     def _sampled_pairs(self):
         pairs = []
@@ -359,7 +352,10 @@ class ArchAdam:
             ops.alpha_two_step(prob, gg, self.m, self.v, pg, pairs, self.lr, self.betas, self.eps, self.steps, self.weight_decay)
         else:
             ops.alpha_full_step(prob, gg, self.m, self.v, pg, self.lr, self.betas, self.eps, self.steps, self.weight_decay)
-        for i, m in enumerate(net.redundant_modules):
+        self._publish(pg)
+
+    def _publish(self, pg):
+        for i, m in enumerate(self.net.redundant_modules):
             m.alpha_prob.grad = pg[i, :m.n_choices]
             m.alpha_version += 1                          # (the update wrote through the flat block: drop the sampling cache)
 

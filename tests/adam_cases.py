@@ -285,7 +285,7 @@ def alpha_case(rows, width, betas, wd):
 
 
 def alpha_restate_step(c, t, state, float_formed=False):
-    """alpha_full_row of mixed.hip in numpy float32: (alpha, m, v) before step t + 1 -> (alpha, m, v, prob_grad) after it."""
+    """alpha_full_row of alpha.hip in numpy float32: (alpha, m, v) before step t + 1 -> (alpha, m, v, prob_grad) after it."""
     live, width = c['live'], c['width']
     a, m, v = state
     b1, b2 = F32(c['betas'][0]), F32(c['betas'][1])
